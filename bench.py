@@ -11,7 +11,10 @@ max-over-ranks of the contract run over a Unix socket between the ranks of the n
 harness of a no-PyTorch product.  `--tp N` instead runs ONE tensor-parallel engine over N ranks
 (BASELINE config 4's mechanics: RCCL + one-shot all-reduce, vllm_rs_amd/runner.py) and reports its tokens/s.
 
-Prints ONE JSON line on rank 0.  Extra legs (not in the timed region): the roofline of the dequant-GEMM family (HIP-event
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times the K steps and prints the line (`value`, `ms_per_step`);
+`--dump-outputs DIR` also writes what the last timed step returned — the generated tokens of the timed steps and the f32 logits of the
+last one — as DIR/tokens.npy and DIR/logits.npy (same arguments = same seeded weights and prompts, so two builds compare output for
+output).  `--full` adds the extra legs (not in the timed region): the host-loop overhead of a step, the roofline of the dequant-GEMM family (HIP-event
 timed launches, rotating layers), bs=32 throughput, long-context decode, p50 TTFT (128 / 2048 / 32768-token prompts, the
 last one cold and with a prefix-cache hit: config 5), the reference-binding path (`ffi_path`: the GEMMs of a layer through
 marlin_4bit_bf16 + vra_rms_norm + vra_silu_mul as the Rust layers would issue them), a Qwen2-7B-AWQ decode line (config 3)
@@ -41,7 +44,10 @@ def parse():
     ap.add_argument("--batch", type=int, default=1, help="decode batch of the timed region (headline: 1)")
     ap.add_argument("--prompt-len", type=int, default=128)
     ap.add_argument("--model", default="llama3-8b-gptq")
-    ap.add_argument("--no-extras", action="store_true", help="skip the roofline / bs=32 / TTFT / ffi / qwen / cpu legs")
+    ap.add_argument("--full", action="store_true", help="after the timed region also run every other leg (step overhead, roofline, bs=32, long context, "
+                                                        "TTFT, ffi, runner IPC, qwen, CPU baselines, full-depth parity); off: the headline figure only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step returned (tokens, logits) as DIR/<name>.npy")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the roofline / bs=32 / TTFT / ffi / qwen / cpu legs")
     ap.add_argument("--no-cpu", action="store_true")
     ap.add_argument("--no-parity", action="store_true", help="skip the full-depth parity leg (the oracle over all layers, ~20 s)")
     ap.add_argument("--no-graph", action="store_true", help="eager launches (rocprofv3 kernel tracing crashes on hipGraph replay)")
@@ -56,8 +62,9 @@ def make_prompts(n, length, vocab, seed=42):
     return [r.integers(1000, vocab - 1000, size=length).astype("uint32") for _ in range(n)]
 
 
-def run_decode(eng, prompts, warmup, steps, sync):
-    """prefill the prompts (untimed), `warmup` decode steps (untimed), then time exactly `steps` steps."""
+def run_decode(eng, prompts, warmup, steps, sync, after=None):
+    """prefill the prompts (untimed), `warmup` decode steps (untimed), then time exactly `steps` steps.  `after` runs behind the timed
+    region, before the requests are drained: the engine still holds the state of the last timed step."""
     rids = [eng.add_request(p, max_tokens=warmup + steps + 8, ignore_eos=True) for p in prompts]
     # all prompts through prefill: the scheduler alternates prefill and decode steps once something is running (A14),
     # so "the first decode step" is not enough for batches whose prompts exceed one prefill step
@@ -69,15 +76,59 @@ def run_decode(eng, prompts, warmup, steps, sync):
     while done < warmup:
         eng.step()
         done += 1
+    had = len(eng.output(rids[0]))
     sync()
     t0 = time.perf_counter()
     ms_events = eng.timed_decode(steps)
     sync()
     dt = time.perf_counter() - t0
     outs = [eng.output(r) for r in rids]
+    if len(outs[0]) - had != steps:
+        raise RuntimeError(f"the timed region ran {len(outs[0]) - had} decode steps, not the {steps} asked for")
+    if after is not None:
+        after()
     while eng.has_unfinished():  # drain
         eng.step()
     return dt, ms_events, outs
+
+
+def run_decode_rounds(eng, prompts, warmup, steps, sync, after=None):
+    """run_decode for ANY number of timed steps: a request ends at the engine's max_model_len, so what one round of requests cannot hold
+    is timed in further rounds (each with its own untimed prefill and warm-up) and the times are added.  -> seconds, event ms, and per
+    prompt the tokens of the timed steps"""
+    import numpy as np
+    room = (eng.ec.max_model_len or eng.cfg["max_position_embeddings"]) - max(len(p) for p in prompts) - warmup - 16
+    if room < 1:
+        raise SystemExit("bench.py: prompt and warm-up leave no room for a timed step below the engine's max_model_len")
+    dt = ms_events = 0.0
+    toks = [[] for _ in prompts]
+    left = steps
+    while left > 0:
+        n = min(left, room)
+        left -= n
+        d, m, outs = run_decode(eng, prompts, warmup, n, sync, after if left == 0 else None)
+        dt, ms_events = dt + d, ms_events + m
+        for t, o in zip(toks, outs):
+            t.append(o[-n:])
+    return dt, ms_events, [np.concatenate(t) for t in toks]
+
+
+DUMP_CAP_BYTES = 60 * 1000 * 1000  # array bytes of one dump: under 64 MB with the .npy headers
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: name -> array as DIR/<name>.npy.  float32 stays float32, everything else becomes float64 (token ids are exact
+    there).  At most 64 MB in all: an array over its share is cut to a fixed, seeded sample of its rows."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    share = DUMP_CAP_BYTES // max(len(arrays), 1)
+    for name, x in arrays.items():
+        x = np.asarray(x)
+        x = np.ascontiguousarray(x, np.float32 if x.dtype == np.float32 else np.float64)
+        if x.nbytes > share:
+            rows = max(1, share // (x.nbytes // x.shape[0]))
+            x = x[np.sort(np.random.default_rng(0).choice(x.shape[0], rows, replace=False))]
+        np.save(os.path.join(path, name + ".npy"), x)
 
 
 def ttft_p50(eng, prompt_len, vocab, batch, reps=5, seed0=100):
@@ -700,6 +751,9 @@ def tp_main(a):
     identical = all(r[1] == res[0][1] for r in res)
     if not identical:
         raise SystemExit(f"bench.py --tp {a.tp}: the ranks disagree on the generated tokens (A21): " + json.dumps([r[1][0][:8] for r in res]))
+    if a.dump_outputs:
+        import numpy as np
+        dump_outputs(a.dump_outputs, {"tokens": np.stack([np.asarray(o)[-a.steps:] for o in res[0][1]])})
     from vllm_rs_amd import _lib
     ngpu = min(a.tp, max(1, _lib.load().vra_device_count()))  # fewer devices than ranks: the ranks SHARE device 0 (functional run, time-sliced)
     rank_bytes = tp_rank_algorithmic_bytes(cfg, a.tp, a.batch)
@@ -767,8 +821,13 @@ def main():
     V = cfg["vocab_size"]
 
     # ---------------- timed region: K decode steps at the headline batch
-    dt, ms_events, outs = run_decode(eng, make_prompts(a.batch, a.prompt_len, V), a.warmup, a.steps, sync)
+    last = {}  # --dump-outputs: the f32 logits of the last timed step, read before the drain steps overwrite them
+    dt, ms_events, outs = run_decode_rounds(eng, make_prompts(a.batch, a.prompt_len, V), a.warmup, a.steps, sync,
+                                            after=(lambda: last.update(logits=eng.last_logits(a.batch))) if a.dump_outputs and rank == 0 else None)
     dt = max_over_ranks(dist, dt)
+    if a.dump_outputs and rank == 0:
+        import numpy as np
+        dump_outputs(a.dump_outputs, {"tokens": np.stack(outs), "logits": last["logits"]})
     tokens = a.batch * a.steps * world  # weak scaling: every rank decodes its own batch, no data-path collective
     line = {
         "metric": "decode tokens/sec (+ p50 TTFT), Llama-3-8B int4, bs=1/32",
@@ -781,7 +840,7 @@ def main():
                    "batch_per_gpu": a.batch},
         "gpu_ms_per_step_events": ms_events / a.steps,
     }
-    if not a.no_graph:
+    if a.full and not a.no_graph:
         # what the GPU alone needs for this step: the same decode graph replayed back to back, no upload / download / host work
         # in between (vra_engine_bench_replay); ms_per_step minus this is what the host loop adds per step
         rp = eng.bench_replay(64)
@@ -789,7 +848,7 @@ def main():
                                  "note": "replay-only = the step's hipGraph launched 64x back to back with frozen metadata; the timed region above runs the full loop "
                                          "(schedule, one upload, graph launch, downloads of tokens and error word, wait, commit) per step"}
 
-    if rank == 0 and not a.no_extras:
+    if rank == 0 and a.full and not a.no_extras:
         # ---------------- roofline of the dequant-GEMM family at the headline batch: every launch of the four GEMV shapes of a
         # layer timed with HIP events on the engine stream (320 launches each, rotating over all layers' weights).  `roofline`
         # is quoted on the TIME-DOMINANT launch (the largest share of the family's time per token); the family figure is the

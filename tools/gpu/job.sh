@@ -1,6 +1,6 @@
 #!/bin/bash
 # One parameterised GPU job script (replaces the per-call scripts of round 5):  gpurun -- bash tools/gpu/job.sh <job> [args...]
-# Several jobs in one call:  bash tools/gpu/job.sh multi "probe" "bench --no-cpu" ...
+# Several jobs in one call:  bash tools/gpu/job.sh multi "probe" "bench nocpu --full --no-cpu" ...
 # Every job writes under gpurun_out/<round>_<job>*; summaries that are evidence get copied into profiles/ afterwards.
 cd "$GRAFT_REPO_ROOT" 2>/dev/null || cd /root/repo
 R=$PWD
@@ -47,7 +47,7 @@ case "$job" in
   profiles)   # rocprofv3 traces + counter passes (tools/collect_profiles.sh)
     ROUND=$RN bash tools/collect_profiles.sh > $O/${RN}_collect.log 2>&1 ;;
   final)      # the round's closing evidence: bench line as the driver runs it, full GPU suite, smoke
-    ( time timeout 900 python bench.py ) > $O/${RN}_bench_default.json 2> $O/${RN}_bench_default.err
+    ( time timeout 900 python bench.py --full ) > $O/${RN}_bench_default.json 2> $O/${RN}_bench_default.err
     ( time timeout 2400 python -m pytest tests -q -m gpu ) > $O/${RN}_final_pytest_gpu.txt 2>&1
     echo "== rc $?" >> $O/${RN}_final_pytest_gpu.txt
     ( timeout 300 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" ) > $O/${RN}_final_smoke.txt 2>&1 ;;
