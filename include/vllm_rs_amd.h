@@ -154,6 +154,22 @@ void vra_wna16_dequant_frag(const void* qweight_tiled, const void* scales, const
 void vra_dense_frag_gemm(const void* x, const void* wd, const void* bias, const void* residual, void* out, int32_t m, int32_t k,
                          int32_t nv, int32_t dual, int32_t dtype, int32_t tile_n, int64_t stream);
 
+/* FP8 E4M3 block-scaled linears (W8A16; reference: LnFp8, src/models/layers/linear.rs:776-1076 — the DeepSeek / Qwen3-FP8 checkpoint
+ * format): weight [n, k] E4M3 bytes, scales (`weight_scale_inv`) [ceil(n/128), k/128] f32 as on disk.  Arithmetic:
+ *   out[m, j] = round( sum_kb scales[j/128, kb] * ( sum_{i in block kb} x[m, i] * w[j, i] )  (+ bias[j]) ),  then round(out + residual);
+ * the weights widen exactly to `dtype`, products and both sums are f32, the same at every row count.  Shapes: k % 128 == 0,
+ * n % 16 == 0, block sizes [128, 128]; anything else is reported through vra_last_error() before any launch.
+ * vra_fp8_repack: checkpoint bytes -> the CDNA4 tile layout (same byte count), once at load. */
+void vra_fp8_repack(const void* weight, void* out, int32_t n, int32_t k, int32_t block_n, int32_t block_k, int64_t stream);
+void vra_fp8_gemm(const void* x, const void* weight_tiled, const float* scales, const void* bias, const void* residual, void* out,
+                  int32_t m, int32_t k, int32_t n, int32_t block_n, int32_t block_k, int32_t dtype, int64_t stream);
+/* gate/up pair with fused SiLU*mul (mlp.rs:451-469): out[m, n] = silu(x.Wg) * (x.Wu), rounding after each reference op. */
+void vra_fp8_gate_up_silu(const void* x, const void* w_gate, const float* s_gate, const void* w_up, const float* s_up, void* out,
+                          int32_t m, int32_t k, int32_t n, int32_t block_n, int32_t block_k, int32_t dtype, int64_t stream);
+
+/* measurement aid: rows (0..32) up to which vra_fp8_gemm / vra_fp8_gate_up_silu take the streaming kernel; default = the measured crossover */
+void vra_debug_set_fp8_decode_max_rows(int32_t rows);
+
 /* candle_nn::RmsNorm::forward as used by NormX (src/models/layers/others.rs:11-29):
  * out[t,:] = x[t,:] * rsqrt(mean(x²)+eps) * w, f32 math, one rounding. */
 void vra_rms_norm(const void* x, const void* weight, void* out, int32_t tokens, int32_t hidden,
@@ -396,7 +412,7 @@ typedef struct vra_model_config {
   double rope_factor, rope_low_freq_factor, rope_high_freq_factor;
   int32_t rope_original_max_position;
   int32_t attention_bias;    /* qkv bias (qwen2 default true, attention.rs:411-415) */
-  int32_t quant_method;      /* 0 none (dense bf16), 1 gptq, 2 awq */
+  int32_t quant_method;      /* 0 none (dense bf16), 1 gptq, 2 awq, 3 fp8 (E4M3 weights, bits 8, group_size 128) */
   int32_t bits, group_size;
   int32_t dtype;             /* VRA_BF16 / VRA_F16 */
   int32_t tie_word_embeddings;

@@ -17,7 +17,8 @@ import numpy as np
 BF16, F16, F32 = 0, 1, 2
 _ST_DTYPES = {"BF16": (np.uint16, "bf16"), "F16": (np.uint16, "f16"), "F32": (np.float32, "f32"), "I32": (np.int32, "i32"),
               "U32": (np.uint32, "u32"), "I64": (np.int64, "i64"), "U8": (np.uint8, "u8"), "I8": (np.int8, "i8"),
-              "U16": (np.uint16, "u16"), "I16": (np.int16, "i16"), "BOOL": (np.uint8, "bool"), "F64": (np.float64, "f64")}
+              "U16": (np.uint16, "u16"), "I16": (np.int16, "i16"), "BOOL": (np.uint8, "bool"), "F64": (np.float64, "f64"),
+              "F8_E4M3": (np.uint8, "f8e4m3")}  # (FP8 weights come back as their bytes: the kernels widen them)
 ARCHS = {"LlamaForCausalLM": "llama", "MistralForCausalLM": "llama", "Qwen2ForCausalLM": "qwen2", "Qwen3ForCausalLM": "qwen3"}
 
 
@@ -75,8 +76,10 @@ def parse_config(cfg_json, dtype=None):
     q = cfg_json.get("quantization_config")
     if q:
         method = q.get("quant_method", "").lower()
+        if method == "fp8":
+            return _parse_fp8(q, out)
         if method not in ("gptq", "awq"):
-            raise ValueError(f"quant_method {method!r} is not on this path (gptq, awq)")
+            raise ValueError(f"quant_method {method!r} is not on this path (gptq, awq, fp8)")
         if q.get("bits", 4) != 4:
             raise ValueError("only 4-bit GPTQ/AWQ checkpoints are supported (wna16.rs:154-160)")
         if q.get("desc_act", False):
@@ -84,6 +87,24 @@ def parse_config(cfg_json, dtype=None):
         if method == "gptq" and q.get("sym", True) is False:
             raise ValueError("asymmetric GPTQ goes through gemm_half_q_half_alt in the reference (f16 only); not wired into the engine")
         out.update(quant_method=method, group_size=q.get("group_size", 128))
+    return out
+
+
+FP8_LINEARS = ("q_proj", "k_proj", "v_proj", "o_proj", "gate_proj", "up_proj", "down_proj")
+
+
+def _parse_fp8(q, out):
+    """block-scaled E4M3 weights with dynamic 16-bit activations (LnFp8, src/models/layers/linear.rs:776-1076; block size
+    default [128, 128], :798-801).  The kernels serve exactly that block size and every one of the seven linears in FP8."""
+    block = q.get("weight_block_size") or [128, 128]
+    if list(block) != [128, 128]:
+        raise ValueError(f"fp8 weight_block_size {block} is not supported (only [128, 128])")
+    if str(q.get("activation_scheme", "dynamic")).lower() == "static":
+        raise ValueError("fp8 activation_scheme 'static' (per-tensor input scales) is not supported")
+    kept = [m for m in (q.get("modules_to_not_convert") or []) + (q.get("ignored_layers") or []) if any(l in m for l in FP8_LINEARS)]
+    if kept:
+        raise ValueError(f"fp8 checkpoints that keep some linears in 16 bits are not supported: {kept[:4]}")
+    out.update(quant_method="fp8", group_size=128, bits=8)
     return out
 
 
@@ -106,6 +127,10 @@ def to_engine_tensor(name, a, kind, model_dtype):
     as 16-bit patterns of the MODEL dtype (scales/bias are f16 on disk even for bf16 models: wna16.rs:97-109)."""
     if kind in ("i32", "u32"):
         return np.ascontiguousarray(a).view(np.uint32)
+    if kind == "f8e4m3":  # FP8 weight bytes, as stored
+        return np.ascontiguousarray(a).view(np.uint8)
+    if kind == "f32" and name.endswith((".weight_scale_inv", ".weight_scale")):  # FP8 block scales stay f32 (applied to f32 partial sums)
+        return np.ascontiguousarray(a, np.float32)
     want = "bf16" if model_dtype == BF16 else "f16"
     if kind == want:
         return np.ascontiguousarray(a)

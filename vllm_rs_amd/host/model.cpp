@@ -13,6 +13,8 @@
 #include "../csrc/scratch.h"
 #include "host_utils.h"
 
+void vra_launch_fp8_fill(void* out, size_t bytes, uint64_t seed, int64_t stream);  // csrc/fp8_gemm.hip: finite E4M3 bytes
+
 // VRA_X_FRAG=0 / vra_debug_set_x_frag(0): steps of 5..32 rows read h row-major in kernel W (no fragment-order copy)
 static int g_x_frag = [] {
   const char* e = getenv("VRA_X_FRAG");
@@ -35,7 +37,8 @@ Model::Model(const vra_model_config& mc, const vra_engine_config& ec) : mc_(mc),
   // layers shard K in whole scale groups and whole 128-row weight tiles)
   if (world_ > 1) {
     const int g = mc.quant_method != 0 ? (mc.group_size > 0 ? mc.group_size : 0) : 0;
-    if (mc.num_heads % world_) tp_error_ = "tensor parallel: num_heads must be divisible by world_size";
+    if (mc.quant_method == 3) tp_error_ = "tensor parallel: fp8 linears (quant_method 3) run on one rank only; the scale grid is not sharded yet";
+    else if (mc.num_heads % world_) tp_error_ = "tensor parallel: num_heads must be divisible by world_size";
     else if (mc.num_kv_heads >= world_ ? mc.num_kv_heads % world_ != 0 : world_ % mc.num_kv_heads != 0)
       tp_error_ = "tensor parallel: kv heads must divide (or be divided by) world_size";
     else if (mc.intermediate_size % world_) tp_error_ = "tensor parallel: intermediate_size must be divisible by world_size";
@@ -69,9 +72,17 @@ bool Model::qlinear_synth(QLinear& l, int K, int N, bool bias, uint64_t seed) {
   // AWQ zeros concentrated on 8 (vra_fill_awq_zeros; uniform nibbles until round 3), scales ~ U(0.002, 0.02), dense weights ~ N(0, 0.02).
   l.K = K;
   l.N = N;
-  l.quant = mc_.quant_method != 0;
+  l.quant = mc_.quant_method == 1 || mc_.quant_method == 2;
   l.awq = mc_.quant_method == 2;
-  if (l.quant) {
+  l.fp8 = mc_.quant_method == 3;
+  if (l.fp8) {  // finite E4M3 bytes in the tile layout directly (iid), block scales ~ U(0.01, 0.03): weights of std ~ 0.02
+    if (K % 128 || N % 16) return error = "fp8 linears need K % 128 == 0 and N % 16 == 0", false;
+    const size_t ns = (size_t)((N + 127) / 128) * (K / 128);
+    if (!(l.w = dalloc((size_t)K * N)) || !(l.f8_scales = (float*)dalloc(ns * 4))) return false;
+    vra_launch_fp8_fill(l.w, (size_t)K * N, seed, 0);
+    vra_fill_uniform(l.f8_scales, (int64_t)ns, seed + 1, 0.01f, 0.03f, VRA_F32, 0);
+    weight_bytes_ += (size_t)K * N + ns * 4;
+  } else if (l.quant) {
     const int g = mc_.group_size > 0 ? mc_.group_size : K;
     const size_t words = (size_t)(K / 8) * N;
     if (!l.w && !(l.w = dalloc(words * 4))) return false;  // (q/k/v: carved out of the layer's fused block)
@@ -97,6 +108,7 @@ bool Model::qlinear_synth(QLinear& l, int K, int N, bool bias, uint64_t seed) {
   return true;
 }
 
+static bool take_err(std::string& error, const char* where);
 static void* upload(Model* m, std::vector<void*>& allocs, const void* host, size_t bytes, std::string& err) {
   void* p = nullptr;
   if (hipMalloc(&p, bytes ? bytes : 16) != hipSuccess) {
@@ -145,7 +157,7 @@ bool Model::init_synthetic(uint64_t seed) {
       vra_fill_normal(L.k_norm, (int64_t)nk, seed + 5001 + l * 2, 1.f, 0.05f, dt_, 0);
     }
     const bool qb = mc_.attention_bias != 0;
-    if (mc_.quant_method != 0) {  // q | k | v tiles contiguous
+    if (mc_.quant_method == 1 || mc_.quant_method == 2) {  // q | k | v tiles contiguous
       const size_t wq = (size_t)(H / 8) * hq_ * D * 4, wk = (size_t)(H / 8) * hkv_ * D * 4;
       if (!(L.qkv_w = dalloc(wq + 2 * wk))) return false;
       L.q.w = L.qkv_w;
@@ -274,6 +286,30 @@ bool Model::load_tensor(const std::string& name, const void* host, const int64_t
       return dst != nullptr;
     };
     const bool sharded = world_ > 1;
+    if (leaf == "weight" && mc_.quant_method == 3) {  // fp8 [N, K] E4M3 bytes: repacked here, the checkpoint-layout copy freed (one rank only)
+      if (elem_bytes != 1 || ndim != 2) return error = name + ": an fp8 model's linear weights are E4M3 bytes [N, K]", false;
+      void* raw = nullptr;
+      if (hipMalloc(&raw, (size_t)(R * Ccols)) != hipSuccess || hipMemcpy(raw, host, (size_t)(R * Ccols), hipMemcpyHostToDevice) != hipSuccess ||
+          !(l.w = dalloc((size_t)(R * Ccols)))) {
+        if (raw) (void)hipFree(raw);
+        return error = name + ": device allocation or copy failed", false;
+      }
+      l.quant = false, l.fp8 = true, l.N = (int)R, l.K = (int)Ccols;
+      vra_fp8_repack(raw, l.w, l.N, l.K, 128, 128, 0);
+      const bool dev_ok = hipDeviceSynchronize() == hipSuccess;
+      (void)hipFree(raw);
+      weight_bytes_ += (size_t)(R * Ccols);
+      if (take_err(error, name.c_str())) return false;
+      return dev_ok ? true : (error = name + ": repack failed", false);
+    }
+    if ((leaf == "weight_scale_inv" || leaf == "weight_scale") && mc_.quant_method == 3) {
+      if (elem_bytes != 4 || ndim != 2) return error = name + ": fp8 block scales are f32 [ceil(N/128), K/128]", false;
+      void* p = nullptr;
+      if (!up1(p, (size_t)(R * Ccols))) return false;
+      l.f8_scales = (float*)p;
+      weight_bytes_ += (size_t)(R * Ccols) * 4;
+      return true;
+    }
     if (leaf == "weight") {  // dense [N, K]: column-parallel shards dim 0, row-parallel dim 1
       l.quant = false;
       int r, c;
@@ -365,6 +401,10 @@ bool Model::finalize_weights() {
     }
     if (l.quant && !l.scales) {
       error = std::string("missing scales: ") + what;
+      return false;
+    }
+    if (mc_.quant_method == 3 && (!l.fp8 || !l.f8_scales)) {
+      error = std::string("fp8 model: missing E4M3 weight or weight_scale_inv: ") + what;
       return false;
     }
     if (l.quant && l.awq && !l.qzeros) {
@@ -462,7 +502,7 @@ bool Model::init_buffers(int max_tokens, int max_seqs) {
   const size_t am_bytes = ((size_t)GEMV_AM_COUNTER + 8) * 8;
   if (!(argmax_ws_ = (unsigned long long*)dalloc(am_bytes)) || hipMemset(argmax_ws_, 0, am_bytes) != hipSuccess) return false;
   if (!(bench_tokens_ = (uint32_t*)dalloc((size_t)max_seqs * 4))) return false;  // launch_gemm(4, ..): the lm_head microbenchmark's tokens
-  if (mc_.quant_method == 0) {
+  if (mc_.quant_method == 0) {  // (fp8: gate/up go through the DUAL launch, no separate gate / up activations)
     if (!(gate_ = dalloc(T * inter_ * es_)) || !(up_ = dalloc(T * inter_ * es_))) return false;
   }
   const size_t ws = vra_paged_attention_decode_workspace_bytes(max_seqs, hq_, mc_.head_dim, vra_rope_table_rows(&mc_));
@@ -590,6 +630,10 @@ bool Model::linear(const QLinear& l0, const void* x, void* out, int M, const voi
   QLinear l = l0;
   if (!with_bias) l.bias = nullptr;
   if (wrote_frag) *wrote_frag = false;
+  if (l.fp8) {  // one arithmetic at every row count: no int4 / dense fused path, no fragment outputs
+    vra_fp8_gemm(x, l.w, l.f8_scales, l.bias, residual, out, M, l.K, l.N, 128, 128, dt_, stream);
+    return !take_err(error, "linear (fp8)");
+  }
   // down_proj of a 5..32-row step on kernel C, leaving its outputs in fragment order as well (the dispatch order of vra_wna16_gemm:
   // kernels E / W and A first — they do not take this shape —, then C)
   if (l.quant && out_frag && M >= 5 && M <= 32 && l.N % 16 == 0 && !vra_gemv_s_fits(1, M, l.K, mc_.group_size, l.N / 16, false) &&
@@ -645,6 +689,12 @@ bool Model::linear_fused_norm(const QLinear* ls, int nl, void* const* outs, cons
   // RMSNorm (NormX::forward, others.rs:11-29) folded into the GEMV prologue when the whole x fits LDS;
   // q/k/v (Separate projections, attention.rs:224-228,660-669) go out in ONE launch.
   const int K = ls[0].K;
+  if (ls[0].fp8) {  // plain RMSNorm, then one FP8 GEMM per projection
+    vra_rms_norm(x, norm_w, xn_, M, K, mc_.rms_norm_eps, dt_, stream);
+    for (int i = 0; i < nl; i++)
+      if (!linear(ls[i], xn_, outs[i], M, nullptr, stream)) return false;
+    return !take_err(error, "norm + linear (fp8)");
+  }
   bool fusable = nl <= GEMV_MAX_SEG && vra_gemv_fits(ls[0].quant, 1, M, K, ls[0].quant ? mc_.group_size : -1);
   for (int i = 1; i < nl; i++) fusable = fusable && ls[i].quant == ls[0].quant && ls[i].K == K;
   if (fusable) {
@@ -772,6 +822,11 @@ bool Model::linear_fused_norm(const QLinear* ls, int nl, void* const* outs, cons
 bool Model::gate_up(const LayerWeights& L, const void* x, const void* norm_w, void* act, int M, int64_t stream) {
   // MLP::forward (mlp.rs:451-469): down(act(gate(x)) * up(x)); gate/up Separate for GPTQ/AWQ (mlp.rs:142-146)
   const int K = L.gate.K, N = L.gate.N;
+  if (L.gate.fp8) {
+    vra_rms_norm(x, norm_w, xn_, M, K, mc_.rms_norm_eps, dt_, stream);
+    vra_fp8_gate_up_silu(xn_, L.gate.w, L.gate.f8_scales, L.up.w, L.up.f8_scales, act, M, K, N, 128, 128, dt_, stream);
+    return !take_err(error, "gate_up (fp8)");
+  }
   if (L.gate.quant) {
     if (vra_gemv_fits(true, 2, M, K, mc_.group_size)) {
       GemvArgs a = {};
@@ -843,7 +898,7 @@ bool Model::gate_up(const LayerWeights& L, const void* x, const void* norm_w, vo
 // decode streams of kernel E (gemv_q4s.cuh)
 // ---------------------------------------------------------------------------------------------
 bool Model::build_decode_streams() {
-  if (mc_.quant_method == 0) return true;
+  if (mc_.quant_method == 0 || mc_.quant_method == 3) return true;  // (kernel E / W streams are int4 only)
   auto one = [&](QLinear& l) {
     if (!l.quant || l.s_um) return true;
     const int g = mc_.group_size > 0 && mc_.group_size < l.K ? mc_.group_size : l.K;
@@ -1226,6 +1281,7 @@ int64_t Model::gemm_algorithmic_bytes(int which, int M) const {
   // K*N/2 (packed) + (K/g)*N*2 (scales) + (K/g)*N/2 (zeros) + M*K*2 (act) + M*N*2 (out)
   auto one = [&](const QLinear& l) -> int64_t {
     const int64_t K = l.K, N = l.N;
+    if (l.fp8) return K * N + ((N + 127) / 128) * (K / 128) * 4 + (int64_t)M * K * 2 + (int64_t)M * N * 2;
     if (!l.quant) return K * N * 2 + (int64_t)M * K * 2 + (int64_t)M * N * 2;
     const int64_t g = mc_.group_size > 0 ? mc_.group_size : K;
     return K * N / 2 + (K / g) * N * 2 + (K / g) * N / 2 + (int64_t)M * K * 2 + (int64_t)M * N * 2;

@@ -20,6 +20,8 @@ namespace vra {
 struct QLinear {
   int K = 0, N = 0;  // local (per-rank) shape
   bool quant = false, awq = false;
+  bool fp8 = false;              // E4M3 block-scaled (quant_method 3): w = tiles of csrc/gemv_f8.cuh, f8_scales; never `quant`
+  float* f8_scales = nullptr;    // [ceil(N/128), K/128] f32 as on disk
   void* w = nullptr;             // quant: tiled words; dense: [N, K] 16-bit
   void* scales = nullptr;        // [K/g, N] model dtype, row-major
   uint32_t* qzeros = nullptr;    // awq raw [K/g, N/8]

@@ -144,6 +144,29 @@ def rms_norm_wna16_gate_up_silu(x, norm_w, eps, qw_g, sc_g, qz_g, qw_u, sc_u, qz
     return out
 
 
+def fp8_weight_repack(weight_dev, n, k, block=(128, 128)):
+    """checkpoint [n, k] E4M3 bytes -> the tile layout vra_fp8_gemm reads; a new device tensor of n * k bytes"""
+    out = DevBuf(n * k)
+    lib().vra_fp8_repack(_ptr(weight_dev), out.ptr, n, k, block[0], block[1], 0)
+    check_error()
+    return out
+
+
+def fp8_gemm(x, weight_tiled, scales, m, k, n, bias=None, residual=None, dtype=BF16, block=(128, 128), out=None):
+    """LnFp8::forward (linear.rs:776-1076) as W8A16: scales [ceil(n/128), k/128] f32 as on disk"""
+    out = out or DevBuf(m * n * 2)
+    lib().vra_fp8_gemm(_ptr(x), _ptr(weight_tiled), _ptr(scales), _ptr(bias), _ptr(residual), out.ptr, m, k, n, block[0], block[1], dtype, 0)
+    check_error()
+    return out
+
+
+def fp8_gate_up_silu(x, w_gate, s_gate, w_up, s_up, m, k, n, dtype=BF16, block=(128, 128), out=None):
+    out = out or DevBuf(m * n * 2)
+    lib().vra_fp8_gate_up_silu(_ptr(x), _ptr(w_gate), _ptr(s_gate), _ptr(w_up), _ptr(s_up), out.ptr, m, k, n, block[0], block[1], dtype, 0)
+    check_error()
+    return out
+
+
 def unpack_indices(qweight_tiled, k, n):
     out = DevBuf(k * n)
     lib().vra_wna16_unpack_indices(_ptr(qweight_tiled), out.ptr, k, n, 0)
