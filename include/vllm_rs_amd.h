@@ -170,6 +170,27 @@ void vra_fp8_gate_up_silu(const void* x, const void* w_gate, const float* s_gate
 /* measurement aid: rows (0..32) up to which vra_fp8_gemm / vra_fp8_gate_up_silu take the streaming kernel; default = the measured crossover */
 void vra_debug_set_fp8_decode_max_rows(int32_t rows);
 
+/* MXFP4 linears (W4A16; reference: LnMxfp4, src/models/layers/linear.rs:1078-1144 — compressed-tensors `mxfp4-pack-quantized`):
+ * weight_packed [n, k/2] bytes (byte i of a row: k = 2i in the low nibble, 2i + 1 in the high one; a code is sign | 2 exponent bits | 1
+ * mantissa bit), weight_scale [n, k/32] E8M0 bytes.  Arithmetic:
+ *   w[j, i] = E2M1(code) * 2^(scale[j, i/32] - 127), exact in `dtype`;  out[m, j] = round( sum_i x[m, i] * w[j, i]  (+ bias[j]) ),  then
+ *   round(out + residual); f32 products and sums, the same at every row count.
+ * PRECONDITION on every scale byte b (so that w is exact): bf16 2 <= b <= 252, f16 114 <= b <= 140; the engine checks it at load.
+ * Shapes: k % 128 == 0, n % 16 == 0; anything else is reported through vra_last_error() before any launch.  Steps above 32 rows widen the
+ * weights into a process-wide scratch first (it cannot grow inside a stream capture: that is reported, never computed wrongly).
+ * vra_mxfp4_repack: checkpoint bytes -> the CDNA4 tile layout (w_tiled n * k / 2 bytes, s_tiled n * k / 32 bytes), once at load. */
+void vra_mxfp4_repack(const void* weight_packed, const void* weight_scale, void* w_tiled, void* s_tiled, int32_t n, int32_t k, int64_t stream);
+void vra_mxfp4_gemm(const void* x, const void* w_tiled, const void* s_tiled, const void* bias, const void* residual, void* out,
+                    int32_t m, int32_t k, int32_t n, int32_t dtype, int64_t stream);
+/* gate/up pair with fused SiLU*mul (mlp.rs:451-469): out[m, n] = silu(x.Wg) * (x.Wu), rounding after each reference op. */
+void vra_mxfp4_gate_up_silu(const void* x, const void* w_gate, const void* s_gate, const void* w_up, const void* s_up, void* out,
+                            int32_t m, int32_t k, int32_t n, int32_t dtype, int64_t stream);
+/* the widening pass alone: tiles -> the 1 KiB fragments vra_dense_frag_gemm reads, unit nb at virtual n-frag vfrag0 + nb * vstride */
+void vra_mxfp4_dequant_frag(const void* w_tiled, const void* s_tiled, void* wd, int32_t k, int32_t n, int32_t dtype,
+                            int32_t vfrag0, int32_t vstride, int64_t stream);
+/* measurement aid: rows (0..32) up to which vra_mxfp4_gemm / vra_mxfp4_gate_up_silu take the decode kernel; default 32 */
+void vra_debug_set_mxfp4_decode_max_rows(int32_t rows);
+
 /* candle_nn::RmsNorm::forward as used by NormX (src/models/layers/others.rs:11-29):
  * out[t,:] = x[t,:] * rsqrt(mean(x²)+eps) * w, f32 math, one rounding. */
 void vra_rms_norm(const void* x, const void* weight, void* out, int32_t tokens, int32_t hidden,
@@ -412,7 +433,7 @@ typedef struct vra_model_config {
   double rope_factor, rope_low_freq_factor, rope_high_freq_factor;
   int32_t rope_original_max_position;
   int32_t attention_bias;    /* qkv bias (qwen2 default true, attention.rs:411-415) */
-  int32_t quant_method;      /* 0 none (dense bf16), 1 gptq, 2 awq, 3 fp8 (E4M3 weights, bits 8, group_size 128) */
+  int32_t quant_method;      /* 0 none (dense bf16), 1 gptq, 2 awq, 3 fp8 (E4M3 weights, bits 8, group_size 128), 4 mxfp4 (bits 4, group_size 32) */
   int32_t bits, group_size;
   int32_t dtype;             /* VRA_BF16 / VRA_F16 */
   int32_t tie_word_embeddings;

@@ -78,8 +78,10 @@ def parse_config(cfg_json, dtype=None):
         method = q.get("quant_method", "").lower()
         if method == "fp8":
             return _parse_fp8(q, out)
+        if method == "mxfp4" or (method == "compressed-tensors" and _is_mxfp4(q)):
+            return _parse_mxfp4(q, out)
         if method not in ("gptq", "awq"):
-            raise ValueError(f"quant_method {method!r} is not on this path (gptq, awq, fp8)")
+            raise ValueError(f"quant_method {method!r} is not on this path (gptq, awq, fp8, mxfp4)")
         if q.get("bits", 4) != 4:
             raise ValueError("only 4-bit GPTQ/AWQ checkpoints are supported (wna16.rs:154-160)")
         if q.get("desc_act", False):
@@ -108,6 +110,26 @@ def _parse_fp8(q, out):
     return out
 
 
+def _is_mxfp4(q):
+    """compressed-tensors: `format` at the top level, of a config group or of its weights contains "mxfp4" (src/utils/config.rs:804-827,872-890)"""
+    groups = [g for g in (q.get("config_groups") or {}).values() if isinstance(g, dict)]
+    fmts = [q.get("format")] + [g.get("format") for g in groups] + [(g.get("weights") or {}).get("format") for g in groups]
+    return any(isinstance(f, str) and "mxfp4" in f for f in fmts)
+
+
+def _parse_mxfp4(q, out):
+    """E2M1 nibbles with one E8M0 scale byte per 32 weights (LnMxfp4, src/models/layers/linear.rs:1078-1144), 16-bit activations.  The
+    kernels serve block 32 and every one of the seven linears in MXFP4; only lm_head may stay in 16 bits."""
+    sizes = [q.get("group_size")] + [(g.get("weights") or {}).get("group_size") for g in (q.get("config_groups") or {}).values() if isinstance(g, dict)]
+    if any(s not in (None, 32) for s in sizes):
+        raise ValueError(f"mxfp4 group_size {[s for s in sizes if s not in (None, 32)][0]} is not supported (only 32)")
+    kept = [m for m in (q.get("ignore") or []) + (q.get("modules_to_not_convert") or []) if "lm_head" not in m]
+    if kept:
+        raise ValueError(f"mxfp4 checkpoints that keep linears other than lm_head in 16 bits are not supported: {kept[:4]}")
+    out.update(quant_method="mxfp4", group_size=32, bits=4)
+    return out
+
+
 def iter_tensors(model_dir):
     """yields (hf_name, array, kind) over every tensor of the checkpoint (sharded or not)."""
     idx = os.path.join(model_dir, "model.safetensors.index.json")
@@ -128,6 +150,8 @@ def to_engine_tensor(name, a, kind, model_dtype):
     if kind in ("i32", "u32"):
         return np.ascontiguousarray(a).view(np.uint32)
     if kind == "f8e4m3":  # FP8 weight bytes, as stored
+        return np.ascontiguousarray(a).view(np.uint8)
+    if kind in ("u8", "i8") and name.endswith((".weight_packed", ".weight_scale", ".blocks", ".scales")):  # MXFP4 nibbles and E8M0 bytes
         return np.ascontiguousarray(a).view(np.uint8)
     if kind == "f32" and name.endswith((".weight_scale_inv", ".weight_scale")):  # FP8 block scales stay f32 (applied to f32 partial sums)
         return np.ascontiguousarray(a, np.float32)

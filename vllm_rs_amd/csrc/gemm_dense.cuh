@@ -74,6 +74,9 @@ struct GemmXArgs {
   float* slabs;
   uint32_t* counters;
   uint32_t* err;
+  // 0: rnd(rnd(acc) + bias), the int4 path's rounding after each reference op; 1: rnd(acc + bias) in f32, ONE rounding — the contract of
+  // the MXFP4 linears, whose decode kernel rounds that way at every row count
+  int bias_in_f32;
 };
 
 static inline size_t gemm_dense_lds_bytes(int bn) {  // the K loop's two buffers, or the epilogue's [256][bn (+ 8)] tile of outputs
@@ -386,8 +389,8 @@ __global__ __launch_bounds__(GX_THREADS, 2) void gemm_dense_kernel(const GemmXAr
         float v[4];
 #pragma unroll
         for (int e = 0; e < 4; e++) {
-          float t = rnd_dt<DT>(acc[i][j][e]);
-          if (biasp) t = rnd_dt<DT>(t + bs[e]);
+          float t = rnd_dt<DT>(a.bias_in_f32 ? acc[i][j][e] + bs[e] : acc[i][j][e]);  // (bs = 0 without a bias)
+          if (biasp && !a.bias_in_f32) t = rnd_dt<DT>(t + bs[e]);
           if (DUAL) {
             const float u = rnd_dt<DT>(acc[i][j + 1][e]);
             const float sl = rnd_dt<DT>(t / (1.0f + expf(-t)));

@@ -40,7 +40,7 @@ __device__ __forceinline__ s16x8 f8x8_to_frag(uint32_t lo, uint32_t hi) {
 }
 
 // ---- load-time repack: checkpoint [N, K] row-major bytes -> tiles.  One thread = one 16-byte lane word.
-__global__ __launch_bounds__(256) void fp8_repack_kernel(const uint8_t* __restrict__ w, u32x4* __restrict__ out, int N, int K) {
+static __global__ __launch_bounds__(256) void fp8_repack_kernel(const uint8_t* __restrict__ w, u32x4* __restrict__ out, int N, int K) {
   const size_t total = (size_t)(N >> 4) * (K >> 6) * 64;
   const size_t o = blockIdx.x * (size_t)256 + threadIdx.x;
   if (o >= total) return;

@@ -14,6 +14,7 @@
 #include "host_utils.h"
 
 void vra_launch_fp8_fill(void* out, size_t bytes, uint64_t seed, int64_t stream);  // csrc/fp8_gemm.hip: finite E4M3 bytes
+void vra_launch_mxfp4_fill(void* w_tiled, void* s_tiled, int n, int k, uint64_t seed, int64_t stream);  // csrc/mxfp4_gemm.hip: iid codes, scale bytes 119 | 120
 
 // VRA_X_FRAG=0 / vra_debug_set_x_frag(0): steps of 5..32 rows read h row-major in kernel W (no fragment-order copy)
 static int g_x_frag = [] {
@@ -38,6 +39,7 @@ Model::Model(const vra_model_config& mc, const vra_engine_config& ec) : mc_(mc),
   if (world_ > 1) {
     const int g = mc.quant_method != 0 ? (mc.group_size > 0 ? mc.group_size : 0) : 0;
     if (mc.quant_method == 3) tp_error_ = "tensor parallel: fp8 linears (quant_method 3) run on one rank only; the scale grid is not sharded yet";
+    else if (mc.quant_method == 4) tp_error_ = "tensor parallel: mxfp4 linears (quant_method 4) run on one rank only; the tiles are not sharded yet";
     else if (mc.num_heads % world_) tp_error_ = "tensor parallel: num_heads must be divisible by world_size";
     else if (mc.num_kv_heads >= world_ ? mc.num_kv_heads % world_ != 0 : world_ % mc.num_kv_heads != 0)
       tp_error_ = "tensor parallel: kv heads must divide (or be divided by) world_size";
@@ -82,6 +84,12 @@ bool Model::qlinear_synth(QLinear& l, int K, int N, bool bias, uint64_t seed) {
     vra_launch_fp8_fill(l.w, (size_t)K * N, seed, 0);
     vra_fill_uniform(l.f8_scales, (int64_t)ns, seed + 1, 0.01f, 0.03f, VRA_F32, 0);
     weight_bytes_ += (size_t)K * N + ns * 4;
+  } else if (mc_.quant_method == 4) {  // iid codes and scale bytes 119 | 120 in the tile layout directly: weights of std ~ 0.02
+    if (K % 128 || N % 16) return error = "mxfp4 linears need K % 128 == 0 and N % 16 == 0", false;
+    l.mx4 = true;
+    if (!(l.w = dalloc((size_t)K * N / 2)) || !(l.mx4_scales = dalloc((size_t)K * N / 32))) return false;
+    vra_launch_mxfp4_fill(l.w, l.mx4_scales, N, K, seed, 0);
+    weight_bytes_ += (size_t)K * N / 2 + (size_t)K * N / 32;
   } else if (l.quant) {
     const int g = mc_.group_size > 0 ? mc_.group_size : K;
     const size_t words = (size_t)(K / 8) * N;
@@ -310,6 +318,39 @@ bool Model::load_tensor(const std::string& name, const void* host, const int64_t
       weight_bytes_ += (size_t)(R * Ccols) * 4;
       return true;
     }
+    if (mc_.quant_method == 4 && (leaf == "weight_packed" || leaf == "blocks" || leaf == "weight_scale" || leaf == "scales")) {
+      // mxfp4: [N, K/2] nibble bytes + [N, K/32] E8M0 bytes, in either order; repacked when both are here, the checkpoint-layout copies freed
+      const bool is_w = leaf == "weight_packed" || leaf == "blocks";
+      if (elem_bytes != 1 || ndim != 2) return error = name + ": mxfp4 tensors are bytes, weight [N, K/2] and scales [N, K/32]", false;
+      const int64_t K = Ccols * (is_w ? 2 : 32);
+      if ((l.mx4_raw_w || l.mx4_raw_s) && (l.N != R || l.K != K)) return error = name + ": shape does not match the other half of the mxfp4 pair", false;
+      if (!is_w) {  // exactness of w * 2^(b - 127) in the model dtype
+        const int lo = dt_ == VRA_BF16 ? 2 : 114, hi = dt_ == VRA_BF16 ? 252 : 140;
+        const uint8_t* b = static_cast<const uint8_t*>(host);
+        for (int64_t i = 0; i < R * Ccols; i++)
+          if (b[i] < lo || b[i] > hi)
+            return error = name + ": scale byte " + std::to_string(b[i]) + " at [" + std::to_string(i / Ccols) + ", " + std::to_string(i % Ccols) + "] is outside " +
+                           std::to_string(lo) + ".." + std::to_string(hi) + ", the range in which mxfp4 weights are exact in " + (dt_ == VRA_BF16 ? "bf16" : "f16"), false;
+      }
+      void*& raw = is_w ? l.mx4_raw_w : l.mx4_raw_s;
+      if (raw) return error = name + ": loaded twice", false;
+      if (!up1(raw, (size_t)(R * Ccols))) return false;  // (owned by allocs_ until the repack)
+      l.quant = false, l.N = (int)R, l.K = (int)K;
+      if (!l.mx4_raw_w || !l.mx4_raw_s) return true;
+      bool ok = (l.w = dalloc((size_t)R * K / 2)) && (l.mx4_scales = dalloc((size_t)R * K / 32));
+      if (ok) vra_mxfp4_repack(l.mx4_raw_w, l.mx4_raw_s, l.w, l.mx4_scales, l.N, l.K, 0);
+      ok = ok && hipDeviceSynchronize() == hipSuccess;
+      for (void** p : {&l.mx4_raw_w, &l.mx4_raw_s}) {
+        allocs_.erase(std::find(allocs_.begin(), allocs_.end(), *p));
+        (void)hipFree(*p);
+        *p = nullptr;
+      }
+      if (take_err(error, name.c_str())) return false;
+      if (!ok) return error = name + ": repack failed", false;
+      l.mx4 = true;
+      weight_bytes_ += (size_t)R * K / 2 + (size_t)R * K / 32;
+      return true;
+    }
     if (leaf == "weight") {  // dense [N, K]: column-parallel shards dim 0, row-parallel dim 1
       l.quant = false;
       int r, c;
@@ -394,6 +435,11 @@ bool Model::finalize_weights() {
           break;
         }
       l.raw_qweight = nullptr;
+    }
+    if (mc_.quant_method == 4 && !l.mx4) {
+      error = std::string("mxfp4 model: missing ") + (l.mx4_raw_w ? "weight_scale / scales" : (l.mx4_raw_s ? "weight_packed / blocks" : "weight_packed and weight_scale")) +
+              ": " + what;
+      return false;
     }
     if (!l.w) {
       error = std::string("missing weight: ") + what;
@@ -537,6 +583,12 @@ bool Model::init_buffers(int max_tokens, int max_seqs) {
         if (dense_shape_ok((int)l, k)) need = std::max(need, dense_bytes((int)l, k));
     if (need) (void)vra_dense_scratch(need, 0);  // (unavailable: the GEMMs keep to the int4 kernels)
   }
+  // mxfp4: every step above 32 rows widens one GEMM's weights into the same scratch (gate | up is the largest: K x 2N 16-bit values);
+  // sized now, so that a captured step never has to grow it
+  if (mc_.quant_method == 4 && max_tokens > 32) {
+    const size_t need = (size_t)mc_.hidden_size * std::max((size_t)hq_ * mc_.head_dim, (size_t)2 * inter_) * 2;
+    if (!vra_dense_scratch(need, 0)) return error = "mxfp4: cannot allocate the scratch for the widened weights of steps above 32 rows", false;
+  }
   // resident dequantised weights for long prefills (model.h wd_res_): opt-in, only for engines whose steps can reach the row rule
   {
     const char* res = getenv("VRA_DENSE_PREFILL_RESIDENT");
@@ -630,6 +682,10 @@ bool Model::linear(const QLinear& l0, const void* x, void* out, int M, const voi
   QLinear l = l0;
   if (!with_bias) l.bias = nullptr;
   if (wrote_frag) *wrote_frag = false;
+  if (l.mx4) {  // as fp8 below: one arithmetic at every row count
+    vra_mxfp4_gemm(x, l.w, l.mx4_scales, l.bias, residual, out, M, l.K, l.N, dt_, stream);
+    return !take_err(error, "linear (mxfp4)");
+  }
   if (l.fp8) {  // one arithmetic at every row count: no int4 / dense fused path, no fragment outputs
     vra_fp8_gemm(x, l.w, l.f8_scales, l.bias, residual, out, M, l.K, l.N, 128, 128, dt_, stream);
     return !take_err(error, "linear (fp8)");
@@ -689,7 +745,7 @@ bool Model::linear_fused_norm(const QLinear* ls, int nl, void* const* outs, cons
   // RMSNorm (NormX::forward, others.rs:11-29) folded into the GEMV prologue when the whole x fits LDS;
   // q/k/v (Separate projections, attention.rs:224-228,660-669) go out in ONE launch.
   const int K = ls[0].K;
-  if (ls[0].fp8) {  // plain RMSNorm, then one FP8 GEMM per projection
+  if (ls[0].fp8 || ls[0].mx4) {  // plain RMSNorm, then one FP8 / MXFP4 GEMM per projection
     vra_rms_norm(x, norm_w, xn_, M, K, mc_.rms_norm_eps, dt_, stream);
     for (int i = 0; i < nl; i++)
       if (!linear(ls[i], xn_, outs[i], M, nullptr, stream)) return false;
@@ -822,6 +878,11 @@ bool Model::linear_fused_norm(const QLinear* ls, int nl, void* const* outs, cons
 bool Model::gate_up(const LayerWeights& L, const void* x, const void* norm_w, void* act, int M, int64_t stream) {
   // MLP::forward (mlp.rs:451-469): down(act(gate(x)) * up(x)); gate/up Separate for GPTQ/AWQ (mlp.rs:142-146)
   const int K = L.gate.K, N = L.gate.N;
+  if (L.gate.mx4) {
+    vra_rms_norm(x, norm_w, xn_, M, K, mc_.rms_norm_eps, dt_, stream);
+    vra_mxfp4_gate_up_silu(xn_, L.gate.w, L.gate.mx4_scales, L.up.w, L.up.mx4_scales, act, M, K, N, dt_, stream);
+    return !take_err(error, "gate_up (mxfp4)");
+  }
   if (L.gate.fp8) {
     vra_rms_norm(x, norm_w, xn_, M, K, mc_.rms_norm_eps, dt_, stream);
     vra_fp8_gate_up_silu(xn_, L.gate.w, L.gate.f8_scales, L.up.w, L.up.f8_scales, act, M, K, N, 128, 128, dt_, stream);
@@ -898,7 +959,7 @@ bool Model::gate_up(const LayerWeights& L, const void* x, const void* norm_w, vo
 // decode streams of kernel E (gemv_q4s.cuh)
 // ---------------------------------------------------------------------------------------------
 bool Model::build_decode_streams() {
-  if (mc_.quant_method == 0 || mc_.quant_method == 3) return true;  // (kernel E / W streams are int4 only)
+  if (mc_.quant_method == 0 || mc_.quant_method >= 3) return true;  // (kernel E / W streams are int4 only)
   auto one = [&](QLinear& l) {
     if (!l.quant || l.s_um) return true;
     const int g = mc_.group_size > 0 && mc_.group_size < l.K ? mc_.group_size : l.K;
@@ -1281,6 +1342,7 @@ int64_t Model::gemm_algorithmic_bytes(int which, int M) const {
   // K*N/2 (packed) + (K/g)*N*2 (scales) + (K/g)*N/2 (zeros) + M*K*2 (act) + M*N*2 (out)
   auto one = [&](const QLinear& l) -> int64_t {
     const int64_t K = l.K, N = l.N;
+    if (l.mx4) return K * N / 2 + N * K / 32 + (int64_t)M * K * 2 + (int64_t)M * N * 2;
     if (l.fp8) return K * N + ((N + 127) / 128) * (K / 128) * 4 + (int64_t)M * K * 2 + (int64_t)M * N * 2;
     if (!l.quant) return K * N * 2 + (int64_t)M * K * 2 + (int64_t)M * N * 2;
     const int64_t g = mc_.group_size > 0 ? mc_.group_size : K;

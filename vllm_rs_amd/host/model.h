@@ -22,6 +22,9 @@ struct QLinear {
   bool quant = false, awq = false;
   bool fp8 = false;              // E4M3 block-scaled (quant_method 3): w = tiles of csrc/gemv_f8.cuh, f8_scales; never `quant`
   float* f8_scales = nullptr;    // [ceil(N/128), K/128] f32 as on disk
+  bool mx4 = false;              // MXFP4 (quant_method 4): w = tiles of csrc/gemv_mx4.cuh, mx4_scales; never `quant`
+  void* mx4_scales = nullptr;    // scale words beside the tiles: [N/16][K/128][16] u32
+  void *mx4_raw_w = nullptr, *mx4_raw_s = nullptr;  // checkpoint-layout halves on the device until both are there (then repacked and freed)
   void* w = nullptr;             // quant: tiled words; dense: [N, K] 16-bit
   void* scales = nullptr;        // [K/g, N] model dtype, row-major
   uint32_t* qzeros = nullptr;    // awq raw [K/g, N/8]

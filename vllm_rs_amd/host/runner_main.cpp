@@ -163,11 +163,33 @@ static bool init_from_json(const std::string& text, Init* out, std::string* err)
     if (q->t == Json::Obj) {
       std::string m = q->str("quant_method", "");
       std::transform(m.begin(), m.end(), m.begin(), ::tolower);
-      mc.quant_method = m == "gptq" ? 1 : (m == "awq" ? 2 : 0);
-      if (!m.empty() && !mc.quant_method) return *err = "quant_method " + m + " is not on this path (gptq, awq)", false;
-      if (q->i64("bits", 4) != 4) return *err = "only 4-bit GPTQ/AWQ checkpoints are supported (wna16.rs:154-160)", false;
-      if (q->boolean("desc_act", false)) return *err = "desc_act=true checkpoints are rejected, as in the reference (utils/mod.rs:1316-1318)", false;
-      mc.group_size = (int)q->i64("group_size", 128);
+      // compressed-tensors whose `format` (top level, a config group's or its weights') contains "mxfp4" is mxfp4 (config.rs:804-827,872-890)
+      bool mx4 = m == "mxfp4";
+      if (m == "compressed-tensors") {
+        mx4 = q->str("format", "").find("mxfp4") != std::string::npos;
+        if (const Json* gs = q->get("config_groups"))
+          if (gs->t == Json::Obj)
+            for (auto& g : gs->o) {
+              if (g.second.t != Json::Obj) continue;
+              const Json* w = g.second.get("weights");
+              mx4 = mx4 || g.second.str("format", "").find("mxfp4") != std::string::npos ||
+                    (w && w->t == Json::Obj && w->str("format", "").find("mxfp4") != std::string::npos);
+            }
+      }
+      if (mx4) {  // every linear but lm_head in MXFP4 (checkpoint.py _parse_mxfp4)
+        if (const Json* ig = q->get("ignore"))
+          if (ig->t == Json::Arr)
+            for (auto& e : ig->a)
+              if (e.t == Json::Str && e.s.find("lm_head") == std::string::npos)
+                return *err = "mxfp4 checkpoints that keep linears other than lm_head in 16 bits are not supported: " + e.s, false;
+        mc.quant_method = 4, mc.bits = 4, mc.group_size = 32;
+      } else {
+        mc.quant_method = m == "gptq" ? 1 : (m == "awq" ? 2 : 0);
+        if (!m.empty() && !mc.quant_method) return *err = "quant_method " + m + " is not on this path (gptq, awq, mxfp4)", false;
+        if (q->i64("bits", 4) != 4) return *err = "only 4-bit GPTQ/AWQ checkpoints are supported (wna16.rs:154-160)", false;
+        if (q->boolean("desc_act", false)) return *err = "desc_act=true checkpoints are rejected, as in the reference (utils/mod.rs:1316-1318)", false;
+        mc.group_size = (int)q->i64("group_size", 128);
+      }
     }
   mc.dtype = req->str("dtype", "BF16") == "F16" ? VRA_F16 : VRA_BF16;
   mc.tie_word_embeddings = c->boolean("tie_word_embeddings", false);
@@ -288,6 +310,8 @@ static void load_safetensors(void* eng, const std::string& path, const vra_model
           if (g[i] != (int32_t)(i / gs)) die(name + ": non-trivial g_idx (act-order) is not supported");
         continue;
       }
+    } else if ((dt == "U8" || dt == "I8") && mc.quant_method == 4) {  // mxfp4 nibble bytes and E8M0 scale bytes, as stored
+      elem = 1;
     } else if (dt == "BF16" || dt == "F16" || dt == "F32") {
       elem = 2;
       if (!((dt == "BF16" && want_bf16) || (dt == "F16" && !want_bf16))) {  // scales / bias are f16 on disk even for bf16 models

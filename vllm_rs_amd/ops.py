@@ -167,6 +167,29 @@ def fp8_gate_up_silu(x, w_gate, s_gate, w_up, s_up, m, k, n, dtype=BF16, block=(
     return out
 
 
+def mxfp4_weight_repack(weight_packed_dev, weight_scale_dev, n, k):
+    """checkpoint [n, k/2] E2M1 bytes + [n, k/32] E8M0 bytes -> (tiles, scale words) as vra_mxfp4_gemm reads them; same byte counts"""
+    w, s = DevBuf(n * k // 2), DevBuf(n * k // 32)
+    lib().vra_mxfp4_repack(_ptr(weight_packed_dev), _ptr(weight_scale_dev), w.ptr, s.ptr, n, k, 0)
+    check_error()
+    return w, s
+
+
+def mxfp4_gemm(x, w_tiled, s_tiled, m, k, n, bias=None, residual=None, dtype=BF16, out=None):
+    """LnMxfp4::forward (linear.rs:1078-1144) as W4A16; scale bytes must keep w exact in `dtype` (bf16 2..252, f16 114..140)"""
+    out = out or DevBuf(m * n * 2)
+    lib().vra_mxfp4_gemm(_ptr(x), _ptr(w_tiled), _ptr(s_tiled), _ptr(bias), _ptr(residual), out.ptr, m, k, n, dtype, 0)
+    check_error()
+    return out
+
+
+def mxfp4_gate_up_silu(x, w_gate, s_gate, w_up, s_up, m, k, n, dtype=BF16, out=None):
+    out = out or DevBuf(m * n * 2)
+    lib().vra_mxfp4_gate_up_silu(_ptr(x), _ptr(w_gate), _ptr(s_gate), _ptr(w_up), _ptr(s_up), out.ptr, m, k, n, dtype, 0)
+    check_error()
+    return out
+
+
 def unpack_indices(qweight_tiled, k, n):
     out = DevBuf(k * n)
     lib().vra_wna16_unpack_indices(_ptr(qweight_tiled), out.ptr, k, n, 0)
