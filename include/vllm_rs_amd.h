@@ -191,6 +191,29 @@ void vra_mxfp4_dequant_frag(const void* w_tiled, const void* s_tiled, void* wd, 
 /* measurement aid: rows (0..32) up to which vra_mxfp4_gemm / vra_mxfp4_gate_up_silu take the decode kernel; default 32 */
 void vra_debug_set_mxfp4_decode_max_rows(int32_t rows);
 
+/* NVFP4 linears (W4A16; reference: LnNvfp4, src/models/layers/linear.rs:1146-1306 — ModelOpt / compressed-tensors NVFP4 checkpoints):
+ * codes [n, k/2] bytes in the MXFP4 nibble order, group scales [n, k/16] OCP E4M3 bytes (one per 16 weights), a per-tensor f32 global
+ * scale g passed as a host value (g = 1 / weight_global_scale, or g = weight_scale_2).  Arithmetic:
+ *   w[j, i] = E2M1(code[j, i]) * E4M3(scale[j, i/16]), exact in bf16 and in f16 for every non-NaN scale byte;
+ *   out[m, j] = round( g * ( sum_i x[m, i] * w[j, i] )  (+ bias[j]) ),  then round(out + residual);
+ *   f32 products and sums, g applied once to the finished sum, ONE rounding, the same at every row count.
+ * PRECONDITIONS: no scale byte is 0x7F / 0xFF (NaN; the engine checks it at load); g is finite (checked here).
+ * Shapes: k % 128 == 0, n % 16 == 0, group 16 only; anything else is reported through vra_last_error() before any launch.  Steps above
+ * 32 rows widen the weights into a process-wide scratch first (it cannot grow inside a stream capture: that is reported, never
+ * computed wrongly).
+ * vra_nvfp4_repack: checkpoint bytes -> the CDNA4 tile layout (w_tiled n * k / 2 bytes, s_tiled n * k / 16 bytes), once at load. */
+void vra_nvfp4_repack(const void* weight_packed, const void* weight_scale, void* w_tiled, void* s_tiled, int32_t n, int32_t k, int64_t stream);
+void vra_nvfp4_gemm(const void* x, const void* w_tiled, const void* s_tiled, float global_scale, const void* bias, const void* residual,
+                    void* out, int32_t m, int32_t k, int32_t n, int32_t dtype, int64_t stream);
+/* gate/up pair with fused SiLU*mul (mlp.rs:451-469): out[m, n] = silu(g_gate * x.Wg) * (g_up * x.Wu), rounding after each reference op. */
+void vra_nvfp4_gate_up_silu(const void* x, const void* w_gate, const void* s_gate, float g_gate, const void* w_up, const void* s_up,
+                            float g_up, void* out, int32_t m, int32_t k, int32_t n, int32_t dtype, int64_t stream);
+/* the widening pass alone: tiles -> the 1 KiB fragments vra_dense_frag_gemm reads (w without g), unit nb at virtual n-frag vfrag0 + nb * vstride */
+void vra_nvfp4_dequant_frag(const void* w_tiled, const void* s_tiled, void* wd, int32_t k, int32_t n, int32_t dtype,
+                            int32_t vfrag0, int32_t vstride, int64_t stream);
+/* measurement aid: rows (0..32) up to which vra_nvfp4_gemm / vra_nvfp4_gate_up_silu take the decode kernel; default 32 */
+void vra_debug_set_nvfp4_decode_max_rows(int32_t rows);
+
 /* candle_nn::RmsNorm::forward as used by NormX (src/models/layers/others.rs:11-29):
  * out[t,:] = x[t,:] * rsqrt(mean(x²)+eps) * w, f32 math, one rounding. */
 void vra_rms_norm(const void* x, const void* weight, void* out, int32_t tokens, int32_t hidden,
@@ -433,7 +456,8 @@ typedef struct vra_model_config {
   double rope_factor, rope_low_freq_factor, rope_high_freq_factor;
   int32_t rope_original_max_position;
   int32_t attention_bias;    /* qkv bias (qwen2 default true, attention.rs:411-415) */
-  int32_t quant_method;      /* 0 none (dense bf16), 1 gptq, 2 awq, 3 fp8 (E4M3 weights, bits 8, group_size 128), 4 mxfp4 (bits 4, group_size 32) */
+  int32_t quant_method;      /* 0 none (dense bf16), 1 gptq, 2 awq, 3 fp8 (E4M3 weights, bits 8, group_size 128), 4 mxfp4 (bits 4, group_size 32),
+                              * 5 nvfp4 (bits 4, group_size 16) */
   int32_t bits, group_size;
   int32_t dtype;             /* VRA_BF16 / VRA_F16 */
   int32_t tie_word_embeddings;

@@ -78,10 +78,12 @@ def parse_config(cfg_json, dtype=None):
         method = q.get("quant_method", "").lower()
         if method == "fp8":
             return _parse_fp8(q, out)
+        if method == "nvfp4" or _is_nvfp4(q, method):  # (before mxfp4, as in the reference: config.rs:804-827)
+            return _parse_nvfp4(q, out)
         if method == "mxfp4" or (method == "compressed-tensors" and _is_mxfp4(q)):
             return _parse_mxfp4(q, out)
         if method not in ("gptq", "awq"):
-            raise ValueError(f"quant_method {method!r} is not on this path (gptq, awq, fp8, mxfp4)")
+            raise ValueError(f"quant_method {method!r} is not on this path (gptq, awq, fp8, mxfp4, nvfp4)")
         if q.get("bits", 4) != 4:
             raise ValueError("only 4-bit GPTQ/AWQ checkpoints are supported (wna16.rs:154-160)")
         if q.get("desc_act", False):
@@ -130,6 +132,32 @@ def _parse_mxfp4(q, out):
     return out
 
 
+def _is_nvfp4(q, method):
+    """modelopt with quant_algo NVFP4 / FP4 (any case; also nested under `quantization`), or compressed-tensors whose `format` (top level,
+    a config group's or its weights') contains "nvfp4" (src/utils/config.rs:763-850).  MLX-style `mode: "nvfp4"` packs differently: rejected."""
+    if method == "modelopt":
+        algo = q.get("quant_algo") or (q.get("quantization") or {}).get("quant_algo")
+        return isinstance(algo, str) and algo.lower() in ("nvfp4", "fp4")
+    groups = [g for g in (q.get("config_groups") or {}).values() if isinstance(g, dict)]
+    fmts = [q.get("format")] + [g.get("format") for g in groups] + [(g.get("weights") or {}).get("format") for g in groups]
+    return method == "compressed-tensors" and any(isinstance(f, str) and "nvfp4" in f for f in fmts)
+
+
+def _parse_nvfp4(q, out):
+    """E2M1 nibbles, one E4M3 scale byte per 16 weights and an f32 scale per tensor (LnNvfp4, src/models/layers/linear.rs:1146-1306),
+    16-bit activations.  The kernels serve group 16 and every one of the seven linears in NVFP4; only lm_head may stay in 16 bits."""
+    nested = q.get("quantization") or {}
+    sizes = [q.get("group_size"), nested.get("group_size")]
+    sizes += [(g.get("weights") or {}).get("group_size") for g in (q.get("config_groups") or {}).values() if isinstance(g, dict)]
+    if any(s not in (None, 16) for s in sizes):
+        raise ValueError(f"nvfp4 group_size {[s for s in sizes if s not in (None, 16)][0]} is not supported (only 16)")
+    kept = [m for k in ("ignore", "modules_to_not_convert", "exclude_modules") for m in (q.get(k) or []) + (nested.get(k) or []) if "lm_head" not in m]
+    if kept:
+        raise ValueError(f"nvfp4 checkpoints that keep linears other than lm_head in 16 bits are not supported: {kept[:4]}")
+    out.update(quant_method="nvfp4", group_size=16, bits=4)
+    return out
+
+
 def iter_tensors(model_dir):
     """yields (hf_name, array, kind) over every tensor of the checkpoint (sharded or not)."""
     idx = os.path.join(model_dir, "model.safetensors.index.json")
@@ -151,8 +179,10 @@ def to_engine_tensor(name, a, kind, model_dtype):
         return np.ascontiguousarray(a).view(np.uint32)
     if kind == "f8e4m3":  # FP8 weight bytes, as stored
         return np.ascontiguousarray(a).view(np.uint8)
-    if kind in ("u8", "i8") and name.endswith((".weight_packed", ".weight_scale", ".blocks", ".scales")):  # MXFP4 nibbles and E8M0 bytes
-        return np.ascontiguousarray(a).view(np.uint8)
+    if kind in ("u8", "i8") and name.endswith((".weight_packed", ".weight_scale", ".blocks", ".scales", "_proj.weight")):
+        return np.ascontiguousarray(a).view(np.uint8)  # MXFP4 / NVFP4 nibbles and scale bytes (ModelOpt calls the NVFP4 codes `.weight`)
+    if kind == "f32" and name.endswith((".weight_global_scale", ".weight_scale_2", ".input_scale", ".input_global_scale")):
+        return np.ascontiguousarray(a, np.float32)  # NVFP4 per-tensor scales stay f32 (applied to the f32 sums)
     if kind == "f32" and name.endswith((".weight_scale_inv", ".weight_scale")):  # FP8 block scales stay f32 (applied to f32 partial sums)
         return np.ascontiguousarray(a, np.float32)
     want = "bf16" if model_dtype == BF16 else "f16"

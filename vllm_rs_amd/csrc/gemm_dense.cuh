@@ -77,6 +77,11 @@ struct GemmXArgs {
   // 0: rnd(rnd(acc) + bias), the int4 path's rounding after each reference op; 1: rnd(acc + bias) in f32, ONE rounding — the contract of
   // the MXFP4 linears, whose decode kernel rounds that way at every row count
   int bias_in_f32;
+  // 1: the finished f32 sum (after the split-K slices have met) is multiplied by acc_scale[0] (DUAL: gate fragments by [0], up fragments
+  // by [1]) in front of the bias — the per-tensor global scale of the NVFP4 linears, which cannot be folded into the 16-bit
+  // fragments without a rounding.  0 (every zero-initialised GemmXArgs): the sums are used as they are.
+  int acc_scale_on;
+  float acc_scale[2];
 };
 
 static inline size_t gemm_dense_lds_bytes(int bn) {  // the K loop's two buffers, or the epilogue's [256][bn (+ 8)] tile of outputs
@@ -389,10 +394,11 @@ __global__ __launch_bounds__(GX_THREADS, 2) void gemm_dense_kernel(const GemmXAr
         float v[4];
 #pragma unroll
         for (int e = 0; e < 4; e++) {
-          float t = rnd_dt<DT>(a.bias_in_f32 ? acc[i][j][e] + bs[e] : acc[i][j][e]);  // (bs = 0 without a bias)
+          const float s = a.acc_scale_on ? acc[i][j][e] * a.acc_scale[0] : acc[i][j][e];
+          float t = rnd_dt<DT>(a.bias_in_f32 ? s + bs[e] : s);  // (bs = 0 without a bias)
           if (biasp && !a.bias_in_f32) t = rnd_dt<DT>(t + bs[e]);
           if (DUAL) {
-            const float u = rnd_dt<DT>(acc[i][j + 1][e]);
+            const float u = rnd_dt<DT>(a.acc_scale_on ? acc[i][j + 1][e] * a.acc_scale[1] : acc[i][j + 1][e]);
             const float sl = rnd_dt<DT>(t / (1.0f + expf(-t)));
             t = sl * u;
           }

@@ -9,7 +9,7 @@ from . import _lib
 from ._lib import EngineConfig, ModelConfig
 
 BF16, F16, F32 = 0, 1, 2
-QUANT = {None: 0, "": 0, "none": 0, "gptq": 1, "awq": 2, "fp8": 3, "mxfp4": 4}
+QUANT = {None: 0, "": 0, "none": 0, "gptq": 1, "awq": 2, "fp8": 3, "mxfp4": 4, "nvfp4": 5}
 ROPE = {None: 0, "": 0, "default": 0, "linear": 1, "llama3": 2, "dynamic": 3, "yarn": 4}
 
 
@@ -36,7 +36,7 @@ def model_config(cfg):
                                            (cfg["max_position_embeddings"] / rs["factor"] if rs.get("factor") else cfg["max_position_embeddings"])),
         rope_yarn_explicit=sum(1 << i for i, k in enumerate(("beta_fast", "beta_slow", "attn_factor", "extrapolation_factor")) if k in rs),
         attention_bias=int(bool(cfg.get("attention_bias"))), quant_method=QUANT[cfg.get("quant_method")],
-        bits=8 if cfg.get("quant_method") == "fp8" else 4, group_size=32 if cfg.get("quant_method") == "mxfp4" else cfg.get("group_size", 128),
+        bits=8 if cfg.get("quant_method") == "fp8" else 4, group_size={"mxfp4": 32, "nvfp4": 16}.get(cfg.get("quant_method")) or cfg.get("group_size", 128),
         dtype=cfg.get("dtype", BF16),
         tie_word_embeddings=int(bool(cfg.get("tie_word_embeddings"))),
         sliding_window=int(cfg.get("sliding_window") or 0))

@@ -3,6 +3,7 @@
 
 #include <hip/hip_runtime.h>
 #include <algorithm>
+#include <cmath>
 #include <math.h>
 #include <stdlib.h>
 #include <string.h>
@@ -15,6 +16,7 @@
 
 void vra_launch_fp8_fill(void* out, size_t bytes, uint64_t seed, int64_t stream);  // csrc/fp8_gemm.hip: finite E4M3 bytes
 void vra_launch_mxfp4_fill(void* w_tiled, void* s_tiled, int n, int k, uint64_t seed, int64_t stream);  // csrc/mxfp4_gemm.hip: iid codes, scale bytes 119 | 120
+float vra_launch_nvfp4_fill(void* w_tiled, void* s_tiled, int n, int k, uint64_t seed, int64_t stream);  // csrc/nvfp4_gemm.hip: iid codes, four scale mantissas; -> g
 
 // VRA_X_FRAG=0 / vra_debug_set_x_frag(0): steps of 5..32 rows read h row-major in kernel W (no fragment-order copy)
 static int g_x_frag = [] {
@@ -40,6 +42,7 @@ Model::Model(const vra_model_config& mc, const vra_engine_config& ec) : mc_(mc),
     const int g = mc.quant_method != 0 ? (mc.group_size > 0 ? mc.group_size : 0) : 0;
     if (mc.quant_method == 3) tp_error_ = "tensor parallel: fp8 linears (quant_method 3) run on one rank only; the scale grid is not sharded yet";
     else if (mc.quant_method == 4) tp_error_ = "tensor parallel: mxfp4 linears (quant_method 4) run on one rank only; the tiles are not sharded yet";
+    else if (mc.quant_method == 5) tp_error_ = "tensor parallel: nvfp4 linears (quant_method 5) run on one rank only; the tiles are not sharded yet";
     else if (mc.num_heads % world_) tp_error_ = "tensor parallel: num_heads must be divisible by world_size";
     else if (mc.num_kv_heads >= world_ ? mc.num_kv_heads % world_ != 0 : world_ % mc.num_kv_heads != 0)
       tp_error_ = "tensor parallel: kv heads must divide (or be divided by) world_size";
@@ -90,6 +93,12 @@ bool Model::qlinear_synth(QLinear& l, int K, int N, bool bias, uint64_t seed) {
     if (!(l.w = dalloc((size_t)K * N / 2)) || !(l.mx4_scales = dalloc((size_t)K * N / 32))) return false;
     vra_launch_mxfp4_fill(l.w, l.mx4_scales, N, K, seed, 0);
     weight_bytes_ += (size_t)K * N / 2 + (size_t)K * N / 32;
+  } else if (mc_.quant_method == 5) {  // iid codes and four E4M3 scale mantissas in the tile layout directly; g brings the weights to std ~ 0.02
+    if (K % 128 || N % 16) return error = "nvfp4 linears need K % 128 == 0 and N % 16 == 0", false;
+    l.nv4 = true;
+    if (!(l.w = dalloc((size_t)K * N / 2)) || !(l.nv4_scales = dalloc((size_t)K * N / 16))) return false;
+    l.nv4_g = vra_launch_nvfp4_fill(l.w, l.nv4_scales, N, K, seed, 0);
+    weight_bytes_ += (size_t)K * N / 2 + (size_t)K * N / 16;
   } else if (l.quant) {
     const int g = mc_.group_size > 0 ? mc_.group_size : K;
     const size_t words = (size_t)(K / 8) * N;
@@ -272,7 +281,7 @@ bool Model::load_tensor(const std::string& name, const void* host, const int64_t
       nshard = mc_.num_kv_heads;
       ishard = rank_ / (world_ / mc_.num_kv_heads);
     }
-    const int64_t R = shape[0], Ccols = ndim > 1 ? shape[1] : 1;
+    const int64_t R = ndim > 0 ? shape[0] : 1, Ccols = ndim > 1 ? shape[1] : 1;
     auto shard_upload = [&](bool shard_rows, bool shard_cols, void*& dst, int* out_r, int* out_c) {
       int64_t r0 = 0, r1 = R, c0 = 0, c1 = Ccols;
       if ((shard_rows && R % nshard) || (shard_cols && Ccols % nshard)) {
@@ -349,6 +358,49 @@ bool Model::load_tensor(const std::string& name, const void* host, const int64_t
       if (!ok) return error = name + ": repack failed", false;
       l.mx4 = true;
       weight_bytes_ += (size_t)R * K / 2 + (size_t)R * K / 32;
+      return true;
+    }
+    if (mc_.quant_method == 5 && (leaf == "input_scale" || leaf == "input_global_scale")) return true;  // (FP4 activations: not this W4A16 path)
+    if (mc_.quant_method == 5 && (leaf == "weight_global_scale" || leaf == "weight_scale_2")) {
+      // nvfp4 global scale, f32 [1] or []: weight_global_scale is a divisor (0 -> g = 1), weight_scale_2 a multiplier (linear.rs:1168-1274)
+      if (elem_bytes != 4 || R * Ccols != 1 || ndim > 1) return error = name + ": the nvfp4 global scale is one f32", false;
+      const float raw = *static_cast<const float*>(host);
+      const float g = leaf == "weight_scale_2" ? raw : (raw == 0.0f ? 1.0f : 1.0f / raw);
+      if (!std::isfinite(g)) return error = name + ": global scale " + std::to_string(raw) + " does not give a finite multiplier", false;
+      l.nv4_g = g;
+      return true;
+    }
+    // nvfp4 codes are `weight_packed` | `blocks`, or under ModelOpt names a one-byte `weight`: routed by method and element size, not by name
+    if (mc_.quant_method == 5 && elem_bytes == 1 &&
+        (leaf == "weight_packed" || leaf == "blocks" || leaf == "weight" || leaf == "weight_scale" || leaf == "scales")) {
+      // [N, K/2] nibble bytes + [N, K/16] E4M3 bytes, in either order; repacked when both are here, the checkpoint-layout copies freed
+      const bool is_w = leaf != "weight_scale" && leaf != "scales";
+      if (ndim != 2) return error = name + ": nvfp4 tensors are bytes, weight [N, K/2] and scales [N, K/16]", false;
+      const int64_t K = Ccols * (is_w ? 2 : 16);
+      if ((l.nv4_raw_w || l.nv4_raw_s) && (l.N != R || l.K != K)) return error = name + ": shape does not match the other half of the nvfp4 pair", false;
+      if (!is_w) {  // every non-NaN E4M3 scale keeps w exact in 16 bits
+        const uint8_t* b = static_cast<const uint8_t*>(host);
+        for (int64_t i = 0; i < R * Ccols; i++)
+          if ((b[i] & 0x7F) == 0x7F)
+            return error = name + ": scale byte " + std::to_string(b[i]) + " at [" + std::to_string(i / Ccols) + ", " + std::to_string(i % Ccols) + "] is an E4M3 NaN", false;
+      }
+      void*& raw = is_w ? l.nv4_raw_w : l.nv4_raw_s;
+      if (raw) return error = name + ": loaded twice", false;
+      if (!up1(raw, (size_t)(R * Ccols))) return false;  // (owned by allocs_ until the repack)
+      l.quant = false, l.N = (int)R, l.K = (int)K;
+      if (!l.nv4_raw_w || !l.nv4_raw_s) return true;
+      bool ok = (l.w = dalloc((size_t)R * K / 2)) && (l.nv4_scales = dalloc((size_t)R * K / 16));
+      if (ok) vra_nvfp4_repack(l.nv4_raw_w, l.nv4_raw_s, l.w, l.nv4_scales, l.N, l.K, 0);
+      ok = ok && hipDeviceSynchronize() == hipSuccess;
+      for (void** p : {&l.nv4_raw_w, &l.nv4_raw_s}) {
+        allocs_.erase(std::find(allocs_.begin(), allocs_.end(), *p));
+        (void)hipFree(*p);
+        *p = nullptr;
+      }
+      if (take_err(error, name.c_str())) return false;
+      if (!ok) return error = name + ": repack failed", false;
+      l.nv4 = true;
+      weight_bytes_ += (size_t)R * K / 2 + (size_t)R * K / 16;
       return true;
     }
     if (leaf == "weight") {  // dense [N, K]: column-parallel shards dim 0, row-parallel dim 1
@@ -438,6 +490,11 @@ bool Model::finalize_weights() {
     }
     if (mc_.quant_method == 4 && !l.mx4) {
       error = std::string("mxfp4 model: missing ") + (l.mx4_raw_w ? "weight_scale / scales" : (l.mx4_raw_s ? "weight_packed / blocks" : "weight_packed and weight_scale")) +
+              ": " + what;
+      return false;
+    }
+    if (mc_.quant_method == 5 && !l.nv4) {
+      error = std::string("nvfp4 model: missing ") + (l.nv4_raw_w ? "weight_scale / scales" : (l.nv4_raw_s ? "weight_packed / weight / blocks" : "the codes and weight_scale")) +
               ": " + what;
       return false;
     }
@@ -585,9 +642,9 @@ bool Model::init_buffers(int max_tokens, int max_seqs) {
   }
   // mxfp4: every step above 32 rows widens one GEMM's weights into the same scratch (gate | up is the largest: K x 2N 16-bit values);
   // sized now, so that a captured step never has to grow it
-  if (mc_.quant_method == 4 && max_tokens > 32) {
+  if ((mc_.quant_method == 4 || mc_.quant_method == 5) && max_tokens > 32) {  // (nvfp4: the same pass, the same sizes)
     const size_t need = (size_t)mc_.hidden_size * std::max((size_t)hq_ * mc_.head_dim, (size_t)2 * inter_) * 2;
-    if (!vra_dense_scratch(need, 0)) return error = "mxfp4: cannot allocate the scratch for the widened weights of steps above 32 rows", false;
+    if (!vra_dense_scratch(need, 0)) return error = "mxfp4 / nvfp4: cannot allocate the scratch for the widened weights of steps above 32 rows", false;
   }
   // resident dequantised weights for long prefills (model.h wd_res_): opt-in, only for engines whose steps can reach the row rule
   {
@@ -686,6 +743,10 @@ bool Model::linear(const QLinear& l0, const void* x, void* out, int M, const voi
     vra_mxfp4_gemm(x, l.w, l.mx4_scales, l.bias, residual, out, M, l.K, l.N, dt_, stream);
     return !take_err(error, "linear (mxfp4)");
   }
+  if (l.nv4) {  // 
+    vra_nvfp4_gemm(x, l.w, l.nv4_scales, l.nv4_g, l.bias, residual, out, M, l.K, l.N, dt_, stream);
+    return !take_err(error, "linear (nvfp4)");
+  }
   if (l.fp8) {  // one arithmetic at every row count: no int4 / dense fused path, no fragment outputs
     vra_fp8_gemm(x, l.w, l.f8_scales, l.bias, residual, out, M, l.K, l.N, 128, 128, dt_, stream);
     return !take_err(error, "linear (fp8)");
@@ -745,7 +806,7 @@ bool Model::linear_fused_norm(const QLinear* ls, int nl, void* const* outs, cons
   // RMSNorm (NormX::forward, others.rs:11-29) folded into the GEMV prologue when the whole x fits LDS;
   // q/k/v (Separate projections, attention.rs:224-228,660-669) go out in ONE launch.
   const int K = ls[0].K;
-  if (ls[0].fp8 || ls[0].mx4) {  // plain RMSNorm, then one FP8 / MXFP4 GEMM per projection
+  if (ls[0].fp8 || ls[0].mx4 || ls[0].nv4) {  // plain RMSNorm, then one FP8 / MXFP4 / NVFP4 GEMM per projection
     vra_rms_norm(x, norm_w, xn_, M, K, mc_.rms_norm_eps, dt_, stream);
     for (int i = 0; i < nl; i++)
       if (!linear(ls[i], xn_, outs[i], M, nullptr, stream)) return false;
@@ -882,6 +943,11 @@ bool Model::gate_up(const LayerWeights& L, const void* x, const void* norm_w, vo
     vra_rms_norm(x, norm_w, xn_, M, K, mc_.rms_norm_eps, dt_, stream);
     vra_mxfp4_gate_up_silu(xn_, L.gate.w, L.gate.mx4_scales, L.up.w, L.up.mx4_scales, act, M, K, N, dt_, stream);
     return !take_err(error, "gate_up (mxfp4)");
+  }
+  if (L.gate.nv4) {
+    vra_rms_norm(x, norm_w, xn_, M, K, mc_.rms_norm_eps, dt_, stream);
+    vra_nvfp4_gate_up_silu(xn_, L.gate.w, L.gate.nv4_scales, L.gate.nv4_g, L.up.w, L.up.nv4_scales, L.up.nv4_g, act, M, K, N, dt_, stream);
+    return !take_err(error, "gate_up (nvfp4)");
   }
   if (L.gate.fp8) {
     vra_rms_norm(x, norm_w, xn_, M, K, mc_.rms_norm_eps, dt_, stream);
@@ -1343,6 +1409,7 @@ int64_t Model::gemm_algorithmic_bytes(int which, int M) const {
   auto one = [&](const QLinear& l) -> int64_t {
     const int64_t K = l.K, N = l.N;
     if (l.mx4) return K * N / 2 + N * K / 32 + (int64_t)M * K * 2 + (int64_t)M * N * 2;
+    if (l.nv4) return K * N / 2 + N * K / 16 + (int64_t)M * K * 2 + (int64_t)M * N * 2;
     if (l.fp8) return K * N + ((N + 127) / 128) * (K / 128) * 4 + (int64_t)M * K * 2 + (int64_t)M * N * 2;
     if (!l.quant) return K * N * 2 + (int64_t)M * K * 2 + (int64_t)M * N * 2;
     const int64_t g = mc_.group_size > 0 ? mc_.group_size : K;

@@ -25,6 +25,10 @@ struct QLinear {
   bool mx4 = false;              // MXFP4 (quant_method 4): w = tiles of csrc/gemv_mx4.cuh, mx4_scales; never `quant`
   void* mx4_scales = nullptr;    // scale words beside the tiles: [N/16][K/128][16] u32
   void *mx4_raw_w = nullptr, *mx4_raw_s = nullptr;  // checkpoint-layout halves on the device until both are there (then repacked and freed)
+  bool nv4 = false;              // NVFP4 (quant_method 5): w = tiles of csrc/gemv_nv4.cuh, nv4_scales, nv4_g; never `quant`
+  void* nv4_scales = nullptr;    // scale words beside the tiles: [N/16][K/128][2][16] u32
+  float nv4_g = 1.0f;            // the tensor's global scale (1 / weight_global_scale, or weight_scale_2; 1 if the checkpoint has neither)
+  void *nv4_raw_w = nullptr, *nv4_raw_s = nullptr;  // as mx4_raw_*
   void* w = nullptr;             // quant: tiled words; dense: [N, K] 16-bit
   void* scales = nullptr;        // [K/g, N] model dtype, row-major
   uint32_t* qzeros = nullptr;    // awq raw [K/g, N/8]

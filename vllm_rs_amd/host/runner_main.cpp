@@ -164,8 +164,30 @@ static bool init_from_json(const std::string& text, Init* out, std::string* err)
       std::string m = q->str("quant_method", "");
       std::transform(m.begin(), m.end(), m.begin(), ::tolower);
       // compressed-tensors whose `format` (top level, a config group's or its weights') contains "mxfp4" is mxfp4 (config.rs:804-827,872-890)
-      bool mx4 = m == "mxfp4";
+      // nvfp4 first, as in the reference: modelopt with quant_algo NVFP4 / FP4 (any case, also nested under `quantization`), or
+      // compressed-tensors whose `format` contains "nvfp4" (config.rs:763-850); MLX-style `mode: "nvfp4"` stays rejected
+      bool mx4 = m == "mxfp4", nv4 = m == "nvfp4";
+      auto lower = [](std::string v) { return std::transform(v.begin(), v.end(), v.begin(), ::tolower), v; };
+      const Json* nested = q->get("quantization");
+      if (m == "modelopt") {
+        std::string algo = lower(q->str("quant_algo", ""));
+        if (algo.empty() && nested && nested->t == Json::Obj) algo = lower(nested->str("quant_algo", ""));
+        nv4 = algo == "nvfp4" || algo == "fp4";
+      }
+      int64_t nv4_group = q->i64("group_size", nested && nested->t == Json::Obj ? nested->i64("group_size", 16) : 16);
       if (m == "compressed-tensors") {
+        nv4 = q->str("format", "").find("nvfp4") != std::string::npos;
+        if (const Json* gs = q->get("config_groups"))
+          if (gs->t == Json::Obj)
+            for (auto& g : gs->o) {
+              if (g.second.t != Json::Obj) continue;
+              const Json* w = g.second.get("weights");
+              const bool wobj = w && w->t == Json::Obj;
+              nv4 = nv4 || g.second.str("format", "").find("nvfp4") != std::string::npos || (wobj && w->str("format", "").find("nvfp4") != std::string::npos);
+              if (wobj && w->i64("group_size", 16) != 16) nv4_group = w->i64("group_size", 16);
+            }
+      }
+      if (m == "compressed-tensors" && !nv4) {
         mx4 = q->str("format", "").find("mxfp4") != std::string::npos;
         if (const Json* gs = q->get("config_groups"))
           if (gs->t == Json::Obj)
@@ -176,7 +198,17 @@ static bool init_from_json(const std::string& text, Init* out, std::string* err)
                     (w && w->t == Json::Obj && w->str("format", "").find("mxfp4") != std::string::npos);
             }
       }
-      if (mx4) {  // every linear but lm_head in MXFP4 (checkpoint.py _parse_mxfp4)
+      if (nv4) {  // group 16, every linear but lm_head in NVFP4 (checkpoint.py _parse_nvfp4)
+        if (nv4_group != 16) return *err = "nvfp4 group_size " + std::to_string(nv4_group) + " is not supported (only 16)", false;
+        for (const Json* holder : {q, nested})
+          for (const char* key : {"ignore", "modules_to_not_convert", "exclude_modules"})
+            if (const Json* ig = holder && holder->t == Json::Obj ? holder->get(key) : nullptr)
+              if (ig->t == Json::Arr)
+                for (auto& e : ig->a)
+                  if (e.t == Json::Str && e.s.find("lm_head") == std::string::npos)
+                    return *err = "nvfp4 checkpoints that keep linears other than lm_head in 16 bits are not supported: " + e.s, false;
+        mc.quant_method = 5, mc.bits = 4, mc.group_size = 16;
+      } else if (mx4) {  // every linear but lm_head in MXFP4 (checkpoint.py _parse_mxfp4)
         if (const Json* ig = q->get("ignore"))
           if (ig->t == Json::Arr)
             for (auto& e : ig->a)
@@ -185,7 +217,7 @@ static bool init_from_json(const std::string& text, Init* out, std::string* err)
         mc.quant_method = 4, mc.bits = 4, mc.group_size = 32;
       } else {
         mc.quant_method = m == "gptq" ? 1 : (m == "awq" ? 2 : 0);
-        if (!m.empty() && !mc.quant_method) return *err = "quant_method " + m + " is not on this path (gptq, awq, mxfp4)", false;
+        if (!m.empty() && !mc.quant_method) return *err = "quant_method " + m + " is not on this path (gptq, awq, mxfp4, nvfp4)", false;
         if (q->i64("bits", 4) != 4) return *err = "only 4-bit GPTQ/AWQ checkpoints are supported (wna16.rs:154-160)", false;
         if (q->boolean("desc_act", false)) return *err = "desc_act=true checkpoints are rejected, as in the reference (utils/mod.rs:1316-1318)", false;
         mc.group_size = (int)q->i64("group_size", 128);
@@ -312,6 +344,11 @@ static void load_safetensors(void* eng, const std::string& path, const vra_model
       }
     } else if ((dt == "U8" || dt == "I8") && mc.quant_method == 4) {  // mxfp4 nibble bytes and E8M0 scale bytes, as stored
       elem = 1;
+    } else if ((dt == "U8" || dt == "I8" || dt == "F8_E4M3") && mc.quant_method == 5) {  // nvfp4 nibble bytes and E4M3 scale bytes, as stored
+      elem = 1;
+    } else if (dt == "F32" && mc.quant_method == 5 && (ends_with(name, ".weight_global_scale") || ends_with(name, ".weight_scale_2") ||
+                                                       ends_with(name, ".input_scale") || ends_with(name, ".input_global_scale"))) {
+      elem = 4;  // nvfp4 per-tensor scales stay f32
     } else if (dt == "BF16" || dt == "F16" || dt == "F32") {
       elem = 2;
       if (!((dt == "BF16" && want_bf16) || (dt == "F16" && !want_bf16))) {  // scales / bias are f16 on disk even for bf16 models

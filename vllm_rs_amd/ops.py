@@ -190,6 +190,29 @@ def mxfp4_gate_up_silu(x, w_gate, s_gate, w_up, s_up, m, k, n, dtype=BF16, out=N
     return out
 
 
+def nvfp4_weight_repack(weight_packed_dev, weight_scale_dev, n, k):
+    """checkpoint [n, k/2] E2M1 bytes + [n, k/16] E4M3 bytes -> (tiles, scale words) as vra_nvfp4_gemm reads them; same byte counts"""
+    w, s = DevBuf(n * k // 2), DevBuf(n * k // 16)
+    lib().vra_nvfp4_repack(_ptr(weight_packed_dev), _ptr(weight_scale_dev), w.ptr, s.ptr, n, k, 0)
+    check_error()
+    return w, s
+
+
+def nvfp4_gemm(x, w_tiled, s_tiled, global_scale, m, k, n, bias=None, residual=None, dtype=BF16, out=None):
+    """LnNvfp4::forward (linear.rs:1146-1306) as W4A16: round(global_scale * (x . w) (+ bias)), w = E2M1 * E4M3 exact in `dtype`"""
+    out = out or DevBuf(m * n * 2)
+    lib().vra_nvfp4_gemm(_ptr(x), _ptr(w_tiled), _ptr(s_tiled), global_scale, _ptr(bias), _ptr(residual), out.ptr, m, k, n, dtype, 0)
+    check_error()
+    return out
+
+
+def nvfp4_gate_up_silu(x, w_gate, s_gate, g_gate, w_up, s_up, g_up, m, k, n, dtype=BF16, out=None):
+    out = out or DevBuf(m * n * 2)
+    lib().vra_nvfp4_gate_up_silu(_ptr(x), _ptr(w_gate), _ptr(s_gate), g_gate, _ptr(w_up), _ptr(s_up), g_up, out.ptr, m, k, n, dtype, 0)
+    check_error()
+    return out
+
+
 def unpack_indices(qweight_tiled, k, n):
     out = DevBuf(k * n)
     lib().vra_wna16_unpack_indices(_ptr(qweight_tiled), out.ptr, k, n, 0)
