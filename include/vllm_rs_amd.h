@@ -214,6 +214,34 @@ void vra_nvfp4_dequant_frag(const void* w_tiled, const void* s_tiled, void* wd, 
 /* measurement aid: rows (0..32) up to which vra_nvfp4_gemm / vra_nvfp4_gate_up_silu take the decode kernel; default 32 */
 void vra_debug_set_nvfp4_decode_max_rows(int32_t rows);
 
+/* Mixture-of-experts block (reference: FusedMoe::forward, src/models/layers/moe.rs — Qwen3-MoE style: softmax scoring, no correction
+ * bias, no expert groups, no shared experts), 16-bit experts.  A caller strings: router GEMM (vra_dense_gemm, f32 out) -> vra_moe_route
+ * -> vra_moe_experts.  Arithmetic: exact 16-bit products, f32 sums; h = round(silu(x.Wg) * (x.Wu)) with ONE rounding;
+ * y = h.Wd stays f32; out[t] = round(sum_j topk_weights[t, j] * y[t, j]) in slot order, then round(out + residual).  No atomics: the
+ * same inputs give the same bits.  Refused before any launch: experts > 256, topk > 8, topk > experts, hidden % 128, inter % 64, a
+ * dtype other than bf16 / f16, a null workspace.
+ * vra_moe_route: f32 logits [tokens, experts] -> softmax over the experts, the topk largest probabilities in descending order (equal
+ *   probabilities: the lower expert index first, as vra_argmax_f32), divided by their sum if norm_topk_prob, times routed_scale.
+ *   topk_weights f32 [tokens, topk], topk_ids u32 [tokens, topk]. */
+void vra_moe_route(const float* router_logits, float* topk_weights, uint32_t* topk_ids, int32_t tokens, int32_t experts, int32_t topk,
+                   int32_t norm_topk_prob, float routed_scale, int64_t stream);
+/* checkpoint tensors stacked over the experts (gate, up [experts, inter, hidden]; down [experts, hidden, inter], row-major) -> the
+ * fragment layouts of DESIGN.md §2, gate and up interleaved; same byte counts (gate_up_tiled: 2 * experts * inter * hidden * 2), once at load. */
+void vra_moe_repack(const void* w_gate, const void* w_up, const void* w_down, void* gate_up_tiled, void* down_tiled, int32_t experts,
+                    int32_t hidden, int32_t inter, int32_t dtype, int64_t stream);
+/* bytes of the workspace vra_moe_experts needs for up to max_tokens tokens per call.  Calls walk their tokens in chunks of 2048, so the
+ * size stops growing there.  0 (and vra_last_error) on a shape the block refuses. */
+int64_t vra_moe_workspace_bytes(int32_t max_tokens, int32_t experts, int32_t topk, int32_t hidden, int32_t inter);
+/* out[tokens, hidden] from x [tokens, hidden], the routing of vra_moe_route (a pair whose id is >= experts is dropped) and the
+ * repacked experts; residual [tokens, hidden] or null.  The per-expert work list is built on the device inside the workspace: no
+ * host read-back, no allocation, capturable.  Chunks of up to 32 tokens take the weight-streaming decode kernels, longer ones the tiled
+ * grouped GEMM. */
+void vra_moe_experts(const void* x, const void* gate_up_tiled, const void* down_tiled, const float* topk_weights, const uint32_t* topk_ids,
+                     const void* residual, void* out, void* workspace, int32_t tokens, int32_t experts, int32_t topk, int32_t hidden,
+                     int32_t inter, int32_t dtype, int64_t stream);
+/* measurement aid: tokens (0..32) up to which vra_moe_experts takes the decode kernels; default 32 */
+void vra_debug_set_moe_decode_max_rows(int32_t rows);
+
 /* candle_nn::RmsNorm::forward as used by NormX (src/models/layers/others.rs:11-29):
  * out[t,:] = x[t,:] * rsqrt(mean(x²)+eps) * w, f32 math, one rounding. */
 void vra_rms_norm(const void* x, const void* weight, void* out, int32_t tokens, int32_t hidden,

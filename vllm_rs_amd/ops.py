@@ -213,6 +213,35 @@ def nvfp4_gate_up_silu(x, w_gate, s_gate, g_gate, w_up, s_up, g_up, m, k, n, dty
     return out
 
 
+def moe_route(router_logits, tokens, experts, topk, norm_topk_prob=True, routed_scale=1.0):
+    """MoeRouting::route without a correction bias (moe.rs:132-147): f32 logits [tokens, experts] -> (weights f32, ids u32), each [tokens, topk]"""
+    w, ids = DevBuf(tokens * topk * 4), DevBuf(tokens * topk * 4)
+    lib().vra_moe_route(_ptr(router_logits), w.ptr, ids.ptr, tokens, experts, topk, int(norm_topk_prob), routed_scale, 0)
+    check_error()
+    return w, ids
+
+
+def moe_weight_repack(w_gate, w_up, w_down, experts, hidden, inter, dtype=BF16):
+    """stacked checkpoint experts (gate, up [E, I, H]; down [E, H, I]) -> (gate_up_tiled, down_tiled) as vra_moe_experts reads them"""
+    gu, dn = DevBuf(2 * experts * inter * hidden * 2), DevBuf(experts * inter * hidden * 2)
+    lib().vra_moe_repack(_ptr(w_gate), _ptr(w_up), _ptr(w_down), gu.ptr, dn.ptr, experts, hidden, inter, dtype, 0)
+    check_error()
+    return gu, dn
+
+
+def moe_experts(x, gate_up_tiled, down_tiled, topk_weights, topk_ids, tokens, experts, topk, hidden, inter, residual=None, dtype=BF16,
+                out=None, workspace=None):
+    """FusedMoe::forward after the router (moe.rs): out[t] = round(sum_j w[t, j] * down_e(silu(gate_e x) * up_e x)), e = ids[t, j]"""
+    out = out or DevBuf(tokens * hidden * 2)
+    if workspace is None:
+        workspace = DevBuf(lib().vra_moe_workspace_bytes(tokens, experts, topk, hidden, inter))
+        check_error()
+    lib().vra_moe_experts(_ptr(x), _ptr(gate_up_tiled), _ptr(down_tiled), _ptr(topk_weights), _ptr(topk_ids), _ptr(residual), out.ptr,
+                          _ptr(workspace), tokens, experts, topk, hidden, inter, dtype, 0)
+    check_error()
+    return out
+
+
 def unpack_indices(qweight_tiled, k, n):
     out = DevBuf(k * n)
     lib().vra_wna16_unpack_indices(_ptr(qweight_tiled), out.ptr, k, n, 0)
