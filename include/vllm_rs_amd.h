@@ -242,6 +242,29 @@ void vra_moe_experts(const void* x, const void* gate_up_tiled, const void* down_
 /* measurement aid: tokens (0..32) up to which vra_moe_experts takes the decode kernels; default 32 */
 void vra_debug_set_moe_decode_max_rows(int32_t rows);
 
+/* The same block on MXFP4 experts (W4A16; reference: FusedMoeMxfp4, src/models/layers/moe.rs): per expert, gate and up [inter, hidden/2]
+ * packed bytes with [inter, hidden/32] E8M0 scale bytes, down [hidden, inter/2] with [hidden, inter/32]; nibble order and code table as
+ * the MXFP4 linears above.  Arithmetic: DESIGN.md §5.4 with w = E2M1(code) * 2^(scale - 127), exact in `dtype` (§5.2) — f32 sums, h
+ * rounded once, y f32, out rounded once over the slots in order, then round(out + residual).  PRECONDITION on every scale byte b, as for
+ * vra_mxfp4_gemm: bf16 2 <= b <= 252, f16 114 <= b <= 140.  Routing comes from vra_moe_route, the workspace from vra_moe_workspace_bytes.
+ * Refused before any launch: everything vra_moe_experts refuses, inter % 128 (the down GEMM walks K in 128-wide tiles), a null scale pointer.
+ * vra_moe_mxfp4_repack: checkpoint tensors stacked over the experts (gate, up packed [experts, inter, hidden/2], scales [experts, inter,
+ *   hidden/32]; down packed [experts, hidden, inter/2], scales [experts, hidden, inter/32]) -> the tile layouts of DESIGN.md §2, once at
+ *   load.  Output bytes: gate_up_tiled experts * inter * hidden, gate_up_scales experts * inter * hidden / 16, down_tiled experts * hidden *
+ *   inter / 2, down_scales experts * hidden * inter / 32 (the byte counts of their inputs; gate and up interleaved tile by tile). */
+void vra_moe_mxfp4_repack(const void* gate_packed, const void* gate_scale, const void* up_packed, const void* up_scale, const void* down_packed,
+                          const void* down_scale, void* gate_up_tiled, void* gate_up_scales, void* down_tiled, void* down_scales,
+                          int32_t experts, int32_t hidden, int32_t inter, int64_t stream);
+/* vra_moe_experts on the tiles and scale words of vra_moe_mxfp4_repack: same arguments otherwise, same semantics (a pair whose id is >=
+ * experts is dropped; residual or null; no host read-back, no allocation, capturable; tokens walked in chunks of 2048).  Chunks of up to
+ * 32 tokens take the weight-streaming MXFP4 decode kernels, longer ones the tiled MXFP4 grouped GEMM; no 16-bit copy of the experts is made. */
+void vra_moe_mxfp4_experts(const void* x, const void* gate_up_tiled, const void* gate_up_scales, const void* down_tiled, const void* down_scales,
+                           const float* topk_weights, const uint32_t* topk_ids, const void* residual, void* out, void* workspace,
+                           int32_t tokens, int32_t experts, int32_t topk, int32_t hidden, int32_t inter, int32_t dtype, int64_t stream);
+/* measurement aid: tokens (0..32) up to which vra_moe_mxfp4_experts takes the decode kernels; default 32 (vra_debug_set_moe_decode_max_rows
+ * governs the 16-bit kernels only) */
+void vra_debug_set_moe_mxfp4_decode_max_rows(int32_t rows);
+
 /* candle_nn::RmsNorm::forward as used by NormX (src/models/layers/others.rs:11-29):
  * out[t,:] = x[t,:] * rsqrt(mean(x²)+eps) * w, f32 math, one rounding. */
 void vra_rms_norm(const void* x, const void* weight, void* out, int32_t tokens, int32_t hidden,

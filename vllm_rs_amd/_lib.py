@@ -119,6 +119,9 @@ def load():
     _sig(lib, "vra_moe_workspace_bytes", c_i64, c_i32, c_i32, c_i32, c_i32, c_i32)
     _sig(lib, "vra_moe_experts", None, P, P, P, P, P, P, P, P, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i64)
     _sig(lib, "vra_debug_set_moe_decode_max_rows", None, c_i32)
+    _sig(lib, "vra_moe_mxfp4_repack", None, P, P, P, P, P, P, P, P, P, P, c_i32, c_i32, c_i32, c_i64)
+    _sig(lib, "vra_moe_mxfp4_experts", None, P, P, P, P, P, P, P, P, P, P, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i64)
+    _sig(lib, "vra_debug_set_moe_mxfp4_decode_max_rows", None, c_i32)
     _sig(lib, "vra_rms_norm", None, P, P, P, c_i32, c_i32, c_f32, c_i32, c_i64)
     _sig(lib, "vra_qk_rms_norm", None, P, P, P, P, c_i32, c_i32, c_i32, c_i32, c_i32, c_f32, c_i32, c_i64)
     _sig(lib, "vra_add_rms_norm", None, P, P, P, P, P, c_i32, c_i32, c_f32, c_i32, c_i64)

@@ -63,7 +63,8 @@ __device__ __forceinline__ float mx4_scale(uint32_t sw, int j) {
 }
 
 // ---- load-time repack: checkpoint rows -> tiles.  One thread = one 16-byte lane word; the first 16 lanes of a tile also write its scale words.
-__global__ __launch_bounds__(256) void mx4_repack_kernel(const uint8_t* __restrict__ w, const uint8_t* __restrict__ sc, u32x4* __restrict__ wt,
+// (static: this header is included by more than one translation unit)
+static __global__ __launch_bounds__(256) void mx4_repack_kernel(const uint8_t* __restrict__ w, const uint8_t* __restrict__ sc, u32x4* __restrict__ wt,
                                                          uint32_t* __restrict__ st, int N, int K) {
   const int KT = K >> 7;
   const size_t total = (size_t)(N >> 4) * KT * 64;

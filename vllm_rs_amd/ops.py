@@ -242,6 +242,30 @@ def moe_experts(x, gate_up_tiled, down_tiled, topk_weights, topk_ids, tokens, ex
     return out
 
 
+def moe_mxfp4_weight_repack(gate_packed, gate_scale, up_packed, up_scale, down_packed, down_scale, experts, hidden, inter):
+    """stacked MXFP4 experts (gate, up [E, I, H/2] + [E, I, H/32]; down [E, H, I/2] + [E, H, I/32]) -> (gate_up_tiled, gate_up_scales,
+    down_tiled, down_scales) as vra_moe_mxfp4_experts reads them"""
+    n = experts * inter * hidden
+    gu, gs, dn, ds = DevBuf(n), DevBuf(n // 16), DevBuf(n // 2), DevBuf(n // 32)
+    lib().vra_moe_mxfp4_repack(_ptr(gate_packed), _ptr(gate_scale), _ptr(up_packed), _ptr(up_scale), _ptr(down_packed), _ptr(down_scale),
+                               gu.ptr, gs.ptr, dn.ptr, ds.ptr, experts, hidden, inter, 0)
+    check_error()
+    return gu, gs, dn, ds
+
+
+def moe_mxfp4_experts(x, gate_up_tiled, gate_up_scales, down_tiled, down_scales, topk_weights, topk_ids, tokens, experts, topk, hidden, inter,
+                      residual=None, dtype=BF16, out=None, workspace=None):
+    """FusedMoeMxfp4::forward after the router (moe.rs): moe_experts on w = E2M1 * 2^(scale - 127); scale bytes must keep w exact in `dtype`"""
+    out = out or DevBuf(tokens * hidden * 2)
+    if workspace is None:
+        workspace = DevBuf(lib().vra_moe_workspace_bytes(tokens, experts, topk, hidden, inter))
+        check_error()
+    lib().vra_moe_mxfp4_experts(_ptr(x), _ptr(gate_up_tiled), _ptr(gate_up_scales), _ptr(down_tiled), _ptr(down_scales), _ptr(topk_weights),
+                                _ptr(topk_ids), _ptr(residual), out.ptr, _ptr(workspace), tokens, experts, topk, hidden, inter, dtype, 0)
+    check_error()
+    return out
+
+
 def unpack_indices(qweight_tiled, k, n):
     out = DevBuf(k * n)
     lib().vra_wna16_unpack_indices(_ptr(qweight_tiled), out.ptr, k, n, 0)
